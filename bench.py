@@ -26,6 +26,14 @@ numpy restatement of the schedule's association before timing.  The N
 independent 1 GiB local reductions of round 1 are reported as an extra
 (`reduce_local_replicas`); the pairwise, pipelined, fused-pull schedules and
 the allreduce are secondary figures under a watchdog.
+
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, warms up, times
+the K steps and prints the headline line: `metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` and the workload's `config`.
+Every other figure or check named above (`roofline`, `cpu_baseline`,
+`host_crossover`, the parity checks, the secondary schedules, ...) is measured
+only with `--full`.  `--dump-outputs DIR` writes what the last timed step left
+in the caller's result buffer to DIR/<name>.npy (see dump_output).
 """
 import argparse
 import ctypes
@@ -51,6 +59,8 @@ HBM_PEAK_GBS = 8000.0       # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 XGMI_LINK_GBS = 153.0       # one xGMI link, one direction (task brief: 7 x ~153 GB/s per GPU)
 GIB = float(1 << 30)
 EXIT_PARITY = 3             # a rank's result failed a bit / closed-form check
+DUMP_SAMPLE_BYTES = 32 << 20    # --dump-outputs: at most this much of one array is written
+DUMP_SEED = 0x5EED0D00          # ... at indices drawn from this seed
 
 
 def parse(argv=None):
@@ -64,12 +74,24 @@ def parse(argv=None):
     p.add_argument('--steps', type=int, default=50)
     p.add_argument('--warmup', type=int, default=5)
     p.add_argument('--count', type=int, default=1 << 28, help='fp32 elements per operand')
+    p.add_argument('--full', action='store_true',
+                   help='everything beside the headline: kernel-only roofline timing, parity '
+                        'checks against the reference association, CPU baselines, triad / '
+                        'end-to-end / crossover / other configs, secondary collectives and the '
+                        'defaults A/B.  Without it a run sets up, warms up, times --steps steps '
+                        'and prints the headline line')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='after the timed steps write what the last timed step left in the '
+                        'caller\'s result buffer as DIR/<name>.npy (float32; a fixed seeded '
+                        'sample of at most %d MiB per array)' % (DUMP_SAMPLE_BYTES >> 20))
     p.add_argument('--cpu-seconds', type=float, default=20.0,
-                   help='bounded CPU-baseline sample duration per leg')
-    p.add_argument('--no-cpu-baseline', action='store_true')
+                   help='--full: bounded CPU-baseline sample duration per leg')
+    p.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
     p.add_argument('--no-extras', action='store_true',
-                   help='skip triad / end-to-end / crossover / secondary collective figures')
-    p.add_argument('--sweep', action='store_true', help='config 2 chunk/size sweep')
+                   help='--full without triad / end-to-end / crossover / secondary collective '
+                        'figures')
+    p.add_argument('--sweep', action='store_true',
+                   help='config 2 chunk/size sweep (needs --full)')
     p.add_argument('--rsb-bytes', type=int, default=4 << 30, help='RSB vector bytes per rank')
     p.add_argument('--extras-timeout', type=float, default=300.0,
                    help='watchdog (s) over the N>1 secondary collective figures and teardown')
@@ -81,7 +103,38 @@ def parse(argv=None):
     p.add_argument('--ab-rounds', type=int, default=2, help='N>1 defaults A/B: interleaved passes')
     p.add_argument('--pmc', default=os.path.join(ROOT, 'profiles', 'r06g_pmc_summary.json'),
                    help='PMC traffic summary (from tools/pmc_summary.py) to quote as traffic')
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.sweep and not args.full:
+        p.error('--sweep is one of the figures behind --full')
+    return args
+
+
+def dump_indices(numel, nbytes=DUMP_SAMPLE_BYTES):
+    """which elements of a `numel`-element fp32 array --dump-outputs writes:
+    None (all of them) when the array fits `nbytes`, else nbytes / 4 indices
+    drawn from a seeded host generator, the first and the last element among
+    them -- the same indices for the same length in every run and every
+    build, so two dumps compare element for element"""
+    k = nbytes // 4
+    if numel <= k:
+        return None
+    g = torch.Generator()
+    g.manual_seed(DUMP_SEED)
+    idx = torch.randint(0, numel, (k,), generator=g)
+    idx[0], idx[1] = 0, numel - 1
+    return idx
+
+
+def dump_output(directory, name, t, nbytes=DUMP_SAMPLE_BYTES):
+    """--dump-outputs: tensor `t` (what the timed path left for its caller) as
+    directory/name.npy in float32, whole or the dump_indices sample of it"""
+    os.makedirs(directory, exist_ok=True)
+    flat = t.reshape(-1)
+    idx = dump_indices(flat.numel(), nbytes)
+    if idx is not None:
+        flat = flat.index_select(0, idx.to(flat.device))
+    np.save(os.path.join(directory, name + '.npy'),
+            flat.to(torch.float32).cpu().numpy())
 
 
 def bench_lib():
@@ -518,7 +571,12 @@ def reduce_local_leg(args, world, rank, dev):
     t = time.perf_counter() - t0
     if world > 1:
         t = allreduce_scalar(t, dist.ReduceOp.MAX, dev)
+    if args.dump_outputs and world == 1:
+        # inout as the last timed step left it, before any later leg folds into it again
+        dump_output(args.dump_outputs, 'reduce_local_inout', inout)
     stream = torch.cuda.current_stream()
+    if not args.full:
+        return dict(t=t, inb=inb, inout=inout, stream=stream)
     kreps = max(10, min(args.steps, 50))
     call = lambda: redop.check(redop.reduce_local_async(inb, inout, n, H.MPI_FLOAT, H.MPI_SUM,  # noqa
                                                          stream))
@@ -548,9 +606,7 @@ def single_gpu(args, dev):
     n = args.count
     nbytes_alg = 3 * n * 4
     leg = reduce_local_leg(args, 1, 0, dev)
-    inb, inout, stream, kreps = leg['inb'], leg['inout'], leg['stream'], leg['kreps']
-    achieved = nbytes_alg / (leg['k_avg'] * 1e-3) / 1e9
-    traffic, traffic_src, traced = load_pmc(args.pmc, n)
+    inb, inout, stream = leg['inb'], leg['inout'], leg['stream']
     result = {
         'metric': METRIC,
         'value': round(nbytes_alg * args.steps / leg['t'] / GIB, 2),
@@ -570,9 +626,18 @@ def single_gpu(args, dev):
             'count': n, 'bytes_per_operand': 4 * n, 'algorithmic_bytes_per_step': nbytes_alg,
             'parallelism': 'single GPU',
             'launch': redop.get_launch(),
-            'store_policy_xcd_mask': {'synchronous_entry': leg['sync_mask'],
-                                      'stream_ordered_entries': leg['async_mask']},
         },
+    }
+    if not args.full:
+        # a plain run: the headline alone (every other figure is behind --full)
+        print(json.dumps(result, default=str), flush=True)
+        return
+    kreps = leg['kreps']
+    achieved = nbytes_alg / (leg['k_avg'] * 1e-3) / 1e9
+    traffic, traffic_src, traced = load_pmc(args.pmc, n)
+    result['config']['store_policy_xcd_mask'] = {'synchronous_entry': leg['sync_mask'],
+                                                 'stream_ordered_entries': leg['async_mask']}
+    result.update({
         'roofline': {
             'bound': 'hbm', 'achieved': round(achieved, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
             'frac': round(achieved / HBM_PEAK_GBS, 4),
@@ -595,7 +660,7 @@ def single_gpu(args, dev):
                                      'back (a stream-ordered caller, with the stream-ordered '
                                      'entries\' store policy, DESIGN.md §8)'},
         },
-    }
+    })
     if traced and traced.get('avg_duration_ns'):
         # the same kernel's rocprofv3 kernel-trace average from the quoted
         # evidence pass, and that run's own step time: frac_traced follows
@@ -1183,16 +1248,17 @@ def multi_gpu(args, world, rank, dev):
               'unit': 'GB/s', 'higher_is_better': True, 'scaling': 'strong', 'vs_baseline': None,
               'dtype': 'f32', 'data': 'synthetic (uniform [-1,1), seeded per rank)',
               'launcher': 'bench.py' if os.environ.get('MPIX_BENCH_LAUNCHED') else 'external'}
-    # the round-1 figure, kept as an extra: N independent 1 GiB local reductions
-    leg = reduce_local_leg(args, world, rank, dev)
-    n = args.count
-    result['reduce_local_replicas'] = dict(
-        value_GiBs=round(world * 3 * n * 4 * args.steps / leg['t'] / GIB, 2),
-        ms_per_step=round(1e3 * leg['t'] / args.steps, 4),
-        kernel_ms_avg_rank0=round(leg['k_avg'], 4),
-        note='every rank reduces its own 1 GiB operands, no collective (round-1 N>1 value)')
-    del leg
-    torch.cuda.empty_cache()
+    if args.full:
+        # the round-1 figure, kept as an extra: N independent 1 GiB local reductions
+        leg = reduce_local_leg(args, world, rank, dev)
+        n = args.count
+        result['reduce_local_replicas'] = dict(
+            value_GiBs=round(world * 3 * n * 4 * args.steps / leg['t'] / GIB, 2),
+            ms_per_step=round(1e3 * leg['t'] / args.steps, 4),
+            kernel_ms_avg_rank0=round(leg['k_avg'], 4),
+            note='every rank reduces its own 1 GiB operands, no collective (round-1 N>1 value)')
+        del leg
+        torch.cuda.empty_cache()
 
     if dist.get_backend() == 'nccl':
         cc = ccl.comm_create_ccl_from_process_group()
@@ -1202,35 +1268,10 @@ def multi_gpu(args, world, rank, dev):
     _CCL['comm'] = cc
     total = (args.rsb_bytes // 4) // world * world
     recvcount = total // world
-    # parity before timing: fp32 SUM at a reduced size, bit for bit against
-    # the schedule's association restated in numpy on every rank, checked
-    # with every half-step's combine split onto the second stream (overlap
-    # threshold 1 byte) and with none split (0).  A failure in either form
-    # fails the run: the shipped default must never be timed unchecked.
-    progress(rank, 'value leg: parity gate')
     shipped_overlap = cc.rh_overlap()
     rc_small = (1 << 16) + 3
-    sends = [rsb_inputs_host(r, world, rc_small) for r in range(world)]
-    ds = torch.from_numpy(sends[rank]).to(dev)
-    dr = torch.empty(rc_small, dtype=torch.float32, device=dev)
-    expected = rh_expected_block(sends, rank, rc_small).tobytes()
-    try:
-        for mode in (1, 0):
-            cc.set_rh_overlap(mode)
-            dr.fill_(float('nan'))
-            redop.check(ccl.reduce_scatter_block(ds, dr, rc_small, H.MPI_FLOAT, H.MPI_SUM, cc,
-                                                 'recursive_halving'), 'MPIX_Reduce_scatter_block')
-            sched = schedule_ran(cc, 'recursive_halving')
-            if 'error' in sched:
-                raise RuntimeError('value leg: recursive halving requested, ' + sched['error'])
-            ok = dr.cpu().numpy().tobytes() == expected
-            if allreduce_scalar(1.0 if ok else 0.0, dist.ReduceOp.MIN, dev) != 1.0:
-                raise ParityError('recursive-halving RSB differs from the reference association '
-                                  '(fp32 SUM, recvcount %d, combine overlap %s) on some rank'
-                                   % (rc_small, 'on every half-step' if mode else 'off'))
-    finally:
-        cc.set_rh_overlap(shipped_overlap)
-    del ds, dr, sends
+    if args.full:
+        rsb_parity_gate(cc, world, rank, dev, rc_small)
 
     send = torch.empty(total, dtype=torch.float32, device=dev)
     fill_uniform(send, 0x5EED0100 + rank)
@@ -1255,6 +1296,69 @@ def multi_gpu(args, world, rank, dev):
     torch.cuda.synchronize()
     dist.barrier()
     t = allreduce_scalar(time.perf_counter() - t0, dist.ReduceOp.MAX, dev) / args.steps
+    sched = schedule_ran(cc, 'recursive_halving')
+    if 'error' in sched:
+        raise RuntimeError('value leg: recursive halving requested, ' + sched['error'])
+    if args.dump_outputs:
+        # every rank's own block of the last timed call; the ranks share the size limit
+        dump_output(args.dump_outputs, 'reduce_scatter_block_recv_rank%d' % rank, recv,
+                    DUMP_SAMPLE_BYTES // world)
+    busbytes = (world - 1) / world * total * 4
+    result.update(
+        value=round(busbytes / t / 1e9, 2),
+        ms_per_step=round(t * 1e3, 4),
+        config={'workload': 'MPI_Reduce_scatter_block(MPI_SUM, MPI_FLOAT), BASELINE configs[3]: '
+                            '4 GiB vector per rank, recursive halving, RCCL/xGMI chunk transport',
+                'vector_bytes_per_rank': total * 4, 'recvcount': recvcount,
+                'parallelism': 'rsb%d (one rank per GPU, libmpix_coll over RCCL)' % world},
+        schedule_ran=sched['schedule_ran'],
+        combine_overlap=overlap_note(shipped_overlap))
+    if args.full:
+        rsb_value_leg_checks(args, result, cc, step, send, recv, t, world, rank, dev, rc_small)
+    del send, recv, ws
+    torch.cuda.empty_cache()
+    return result
+
+
+def rsb_parity_gate(cc, world, rank, dev, rc_small):
+    """--full, before the value leg is timed: the schedule's bits at a reduced size"""
+    from mpich_amd import ccl
+    # parity before timing: fp32 SUM at a reduced size, bit for bit against
+    # the schedule's association restated in numpy on every rank, checked
+    # with every half-step's combine split onto the second stream (overlap
+    # threshold 1 byte) and with none split (0).  A failure in either form
+    # fails the run: the shipped default must never be timed unchecked.
+    progress(rank, 'value leg: parity gate')
+    shipped_overlap = cc.rh_overlap()
+    sends = [rsb_inputs_host(r, world, rc_small) for r in range(world)]
+    ds = torch.from_numpy(sends[rank]).to(dev)
+    dr = torch.empty(rc_small, dtype=torch.float32, device=dev)
+    expected = rh_expected_block(sends, rank, rc_small).tobytes()
+    try:
+        for mode in (1, 0):
+            cc.set_rh_overlap(mode)
+            dr.fill_(float('nan'))
+            redop.check(ccl.reduce_scatter_block(ds, dr, rc_small, H.MPI_FLOAT, H.MPI_SUM, cc,
+                                                 'recursive_halving'), 'MPIX_Reduce_scatter_block')
+            sched = schedule_ran(cc, 'recursive_halving')
+            if 'error' in sched:
+                raise RuntimeError('value leg: recursive halving requested, ' + sched['error'])
+            ok = dr.cpu().numpy().tobytes() == expected
+            if allreduce_scalar(1.0 if ok else 0.0, dist.ReduceOp.MIN, dev) != 1.0:
+                raise ParityError('recursive-halving RSB differs from the reference association '
+                                  '(fp32 SUM, recvcount %d, combine overlap %s) on some rank'
+                                   % (rc_small, 'on every half-step' if mode else 'off'))
+    finally:
+        cc.set_rh_overlap(shipped_overlap)
+    del ds, dr, sends
+
+
+def rsb_value_leg_checks(args, result, cc, step, send, recv, t, world, rank, dev, rc_small):
+    """--full, after the value leg is timed: its result checked at the timed
+    size, the per-step breakdown, the defaults A/B and the CPU baseline"""
+    recvcount = recv.numel()
+    total = world * recvcount
+    shipped_overlap = cc.rh_overlap()
     # the timed calls' own result, at the timed size, on every rank (VERDICT
     # r05 item 1): `send` never changes, so `recv` holds one call's block;
     # it must equal the recursive-halving association of every rank's seeded
@@ -1298,12 +1402,6 @@ def multi_gpu(args, world, rank, dev):
     combined = (pof2 - 1) / pof2 * total            # elements this rank combined (pof2 ranks)
     comb_gbs = 3 * combined * 4 / (comb_ms * 1e-3) / 1e9 if comb_ms > 0 else None
     result.update(
-        value=round(busbytes / t / 1e9, 2),
-        ms_per_step=round(t * 1e3, 4),
-        config={'workload': 'MPI_Reduce_scatter_block(MPI_SUM, MPI_FLOAT), BASELINE configs[3]: '
-                            '4 GiB vector per rank, recursive halving, RCCL/xGMI chunk transport',
-                'vector_bytes_per_rank': total * 4, 'recvcount': recvcount,
-                'parallelism': 'rsb%d (one rank per GPU, libmpix_coll over RCCL)' % world},
         parity=dict(checked=True, recvcount=rc_small, bit_exact_all_ranks=True,
                     combine_overlap_checked=['every half-step split', 'none split'],
                     against='numpy restatement of the recursive-halving association',
@@ -1316,8 +1414,6 @@ def multi_gpu(args, world, rank, dev):
                                       'seeded vector regenerated on the device '
                                       '(bench.rh_expected_block_device), torch.equal on the '
                                       'int32 view, MIN over ranks'),
-        schedule_ran=sched['schedule_ran'],
-        combine_overlap=overlap_note(shipped_overlap),
         roofline={'bound': 'hbm', 'unit': 'GB/s',
                   'achieved': round(comb_gbs, 1) if comb_gbs else None, 'peak': HBM_PEAK_GBS,
                   'frac': round(comb_gbs / HBM_PEAK_GBS, 4) if comb_gbs else None,
@@ -1334,9 +1430,6 @@ def multi_gpu(args, world, rank, dev):
         defaults_ab=ab)
     if cpu is not None:
         result['cpu_baseline'] = dict(value=round(busbytes / cpu.pop('value_s') / 1e9, 3), **cpu)
-    del send, recv, ws
-    torch.cuda.empty_cache()
-    return result
 
 
 def host_memory_budget():
@@ -1884,9 +1977,9 @@ def launch_ranks(n, argv):
 
 def dry_run(world, rank, args=None):
     """the launch path without a GPU: ranks rendezvous over gloo, count
-    themselves with an all-reduce, run the N > 1 line's CPU baseline (the
-    reference schedule's host work, unless --no-cpu-baseline) and rank 0
-    prints the line's skeleton"""
+    themselves with an all-reduce, with --full run the N > 1 line's CPU
+    baseline (the reference schedule's host work, unless --no-cpu-baseline)
+    and rank 0 prints the line's skeleton"""
     seen = 1
     cpu = None
     if world > 1:
@@ -1895,7 +1988,7 @@ def dry_run(world, rank, args=None):
         dist.all_reduce(t)
         seen = int(t.item())
         dist.barrier()
-        if args is not None and not args.no_cpu_baseline:
+        if args is not None and args.full and not args.no_cpu_baseline:
             total = (args.rsb_bytes // 4) // world * world
             cpu = rsb_cpu_baseline(world, rank, total // world, None)
             cpu = dict(value=round((world - 1) / world * total * 4 / cpu.pop('value_s') / 1e9, 3),
@@ -1966,7 +2059,7 @@ def main(argv=None):
     emit = _Emitter(rank, result)
     dog = _watchdog(args.extras_timeout, emit)
     result['extras_timeout_s'] = args.extras_timeout
-    failed, code = (None, 0) if args.no_extras else run_secondary(
+    failed, code = (None, 0) if args.no_extras or not args.full else run_secondary(
         result, ((k, lambda part, fn=fn: fn(args, world, rank, dev, part))
                  for k, fn in (('reduce_scatter_block_other', rsb_secondary),
                                ('allreduce', allreduce_secondary))))

@@ -413,7 +413,7 @@ def test_dry_run_line_carries_the_rsb_cpu_baseline(launch):
     recursive-halving host work (copy in, log2(P) combines through the oracle
     loop, copy out) on one pinned core per rank, max over ranks"""
     import json
-    args = ['--gpus', '2', '--dry-run', '--no-extras', '--rsb-bytes', str(16 << 20)]
+    args = ['--gpus', '2', '--dry-run', '--full', '--no-extras', '--rsb-bytes', str(16 << 20)]
     p = _bench(args) if launch == 'bench' else _torchrun(2, args)
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith('{')][0])
@@ -473,3 +473,48 @@ def test_cpu_baseline_reads_reduce_and_triad_from_the_same_passes(oracle):
     else:
         assert 'frac_of_host_triad_per_pass' in c['allcores']
         assert 0 < c['allcores']['frac_of_host_triad'] < 3
+
+
+# ------------------------------------------- plain runs, --full, --dump-outputs
+def test_full_is_off_by_default_and_gates_the_sweep(capsys):
+    import bench
+    assert bench.parse(['--gpus', '1', '--steps', '3', '--warmup', '1']).full is False
+    assert bench.parse(['--full', '--sweep']).sweep is True
+    with pytest.raises(SystemExit):
+        bench.parse(['--sweep'])
+    assert '--full' in capsys.readouterr().err
+
+
+def test_plain_dry_run_runs_no_cpu_baseline():
+    """without --full the N > 1 dry run times nothing: its skeleton carries no
+    CPU baseline (test_dry_run_line_carries_the_rsb_cpu_baseline has the
+    --full form)"""
+    import json
+    p = _bench(['--gpus', '2', '--dry-run', '--rsb-bytes', str(16 << 20)])
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith('{')][0])
+    assert d['n_gpus'] == 2 and d['ranks_seen'] == 2 and d['cpu_baseline'] is None, d
+
+
+def test_dump_output_whole_and_sampled(tmp_path):
+    """--dump-outputs: float32 .npy, whole when it fits the limit, else a
+    sample at indices that depend on the length alone (so two runs, or two
+    builds, write the same elements) and keep the first and last element"""
+    import torch
+    import bench
+    x = torch.arange(1000, dtype=torch.float32) * 0.5
+    assert bench.dump_indices(1000) is None
+    bench.dump_output(str(tmp_path / 'd'), 'whole', x)
+    got = np.load(tmp_path / 'd' / 'whole.npy')
+    assert got.dtype == np.float32 and got.tobytes() == x.numpy().tobytes()
+    idx = bench.dump_indices(1000, 256)
+    assert idx.shape == (64,) and idx[0] == 0 and idx[1] == 999
+    assert 0 <= int(idx.min()) and int(idx.max()) < 1000
+    assert torch.equal(idx, bench.dump_indices(1000, 256))
+    bench.dump_output(str(tmp_path / 'd'), 'part', x, 256)
+    got = np.load(tmp_path / 'd' / 'part.npy')
+    assert got.dtype == np.float32 and got.nbytes == 256
+    assert got.tobytes() == x[idx].numpy().tobytes()
+    # the default limit keeps one array, and the N > 1 ranks' shares, within 64 MB
+    assert bench.DUMP_SAMPLE_BYTES <= 32 << 20
+    assert bench.dump_indices((1 << 28), bench.DUMP_SAMPLE_BYTES).numel() * 4 <= 32 << 20

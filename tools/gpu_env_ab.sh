@@ -16,7 +16,7 @@ for i in 1 2; do
             >> $O/types.jsonl 2>> $O/types.err || exit 1
         env $settings timeout -k 10 120 python3 tools/multi_probe.py --ks 1,3,7,15 --tree-ks 2,4,8,16 \
             > $O/multi_${v}_$i.json 2>> $O/multi.err || exit 1
-        env $settings timeout -k 10 400 python3 bench.py --no-cpu-baseline > $O/bench_${v}_$i.json \
+        env $settings timeout -k 10 400 python3 bench.py --full --no-cpu-baseline > $O/bench_${v}_$i.json \
             2> $O/bench_${v}_$i.err || exit 1
     done
 done

@@ -10,7 +10,7 @@ R=${R:-r03}
 O=gpurun_out/ev_$R
 rm -rf $O && mkdir -p $O
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -T -d $O/kt -o kt --output-format csv -- \
-    python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras > $O/prof_bench.json 2> $O/prof_bench.err && \
+    python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extras > $O/prof_bench.json 2> $O/prof_bench.err && \
 timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE -T -d $O/fetch -o fetch --output-format csv -- \
     python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-extras > /dev/null 2> $O/pmc_fetch.err && \
 timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE -T -d $O/write -o write --output-format csv -- \
@@ -21,7 +21,7 @@ python3 tools/pmc_summary.py --kt "$(find $O/kt -name '*kernel_stats.csv' | head
     --out $O/${R}_pmc_summary.json --stats-copy $O/${R}_rocprof_kernel_stats.csv \
     --trace "$(find $O/kt -name '*kernel_trace.csv' | head -n 1)" \
     --traced-line $O/prof_bench.json > /dev/null && \
-timeout -k 10 500 python3 bench.py --pmc $O/${R}_pmc_summary.json > $O/bench.json 2> $O/bench.err
+timeout -k 10 500 python3 bench.py --full --pmc $O/${R}_pmc_summary.json > $O/bench.json 2> $O/bench.err
 rc=$?
 echo rc=$rc
 cat $O/${R}_pmc_summary.json

@@ -36,7 +36,7 @@ for mode in $MODES; do
     if [ "${LAUNCH:-self}" = torchrun ]; then
         L="python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $P --master-addr 127.0.0.1 --master-port 29517"
     fi
-    MPIX_BENCH_SAME_DEVICE=1 MPIX_BENCH_BACKEND=gloo timeout -k 10 ${LIMIT:-500} $L bench.py --gpus $P \
+    MPIX_BENCH_SAME_DEVICE=1 MPIX_BENCH_BACKEND=gloo timeout -k 10 ${LIMIT:-500} $L bench.py --gpus $P --full \
         --steps $STEPS --warmup 1 --ab-reps 1 --count 67108864 --rsb-bytes $RSB $BENCH_ARGS \
         > $O/n${P}_$mode.json 2> $O/n${P}_$mode.err
     rc=$?

@@ -59,7 +59,7 @@ for step in "$@"; do
                       "$(find $O/pm_fetch -name '*counter_collection.csv' | head -n 1)" \
                       "$(find $O/pm_write -name '*counter_collection.csv' | head -n 1)" \
                       $O/r04_pmc_multi.json || exit $? ;;
-        bench) run bench 600 python3 bench.py || exit $? ;;
+        bench) run bench 600 python3 bench.py --full || exit $? ;;
         pmctree) run pmctree_fetch 180 rocprofv3 --pmc FETCH_SIZE -T -d $O/pt_fetch -o f \
                      --output-format csv -- python3 tools/multi_probe.py --ks 7 --tree-ks 8,16 || exit $?
                  run pmctree_write 180 rocprofv3 --pmc WRITE_SIZE -T -d $O/pt_write -o w \

@@ -14,7 +14,7 @@ for i in $(seq 1 ${N:-3}); do
     for m in ${MASKS:-default 0x88}; do
         if [ $m = default ]; then unset MPIX_REDOP_WT_XCD_SYNC; else export MPIX_REDOP_WT_XCD_SYNC=$m; fi
         echo "run $i sync mask $m ($(date +%T))"
-        timeout -k 10 200 python3 bench.py --no-extras --no-cpu-baseline --steps 100 \
+        timeout -k 10 200 python3 bench.py --full --no-extras --no-cpu-baseline --steps 100 \
             > $O/bench_${m}_$i.json 2> $O/bench_${m}_$i.err || exit 1
     done
 done

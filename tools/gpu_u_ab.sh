@@ -26,7 +26,7 @@ for i in 1 2; do
         lib=mpich_amd/libmpix_redop_alt.so; [ $v = shipped ] && lib=$O/../shipped.so.keep
         cp $lib mpich_amd/libmpix_redop.so
         echo "bench $v run $i ($(date +%T))"
-        timeout -k 10 400 python3 bench.py --no-cpu-baseline > $O/bench_${v}_$i.json 2> $O/bench_${v}_$i.err || exit 1
+        timeout -k 10 400 python3 bench.py --full --no-cpu-baseline > $O/bench_${v}_$i.json 2> $O/bench_${v}_$i.err || exit 1
     done
 done
 cp $O/../shipped.so.keep mpich_amd/libmpix_redop.so

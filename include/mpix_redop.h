@@ -23,6 +23,9 @@
  *                               with the table of src/mpi/datatype/typeutil.c:29-109
  *   MPIX_Reduce_local_vector <- typerep_op_fallback on an MPI_Type_vector target
  *                               src/mpi/datatype/typerep/src/typerep_op.c:69-155
+ *   MPIX_Get_accumulate_local <- the local step of MPI_Get_accumulate / MPI_Fetch_and_op:
+ *                               MPIR_Localcopy + MPIDI_POSIX_compute_accumulate,
+ *                               src/mpid/ch4/shm/posix/posix_rma.h:366-375, 756-767
  *   MPIX_Redop_set_fortran_booleans <- MPIR_Abi_set_fortran_booleans_impl
  *                               src/mpi/datatype/typeutil.c:502-515
  *
@@ -183,6 +186,57 @@ int MPIX_Reduce_local_vector_async(const void *inbuf, void *inoutbuf, MPIX_Aint 
 int MPIX_Reduce_local_vector(const void *inbuf, void *inoutbuf, MPIX_Aint count,
                              MPIX_Aint blocklen, MPIX_Aint stride,
                              MPIX_Datatype basic_type, MPIX_Op op);
+
+/* ---- fused get-accumulate ----
+ * The local step of MPI_Get_accumulate, MPI_Fetch_and_op (count 1), MPI_Get
+ * with MPI_NO_OP and a swap with MPI_REPLACE: for i < count elements of
+ * `datatype` at extent stride
+ *     result[i] = target[i]                  (the value before the call)
+ *     target[i] = target[i] OP origin[i]
+ * as one stream-ordered step that reads the target once -- the reference
+ * copies the target into the result and then applies the op under one lock
+ * (posix_rma.h:366-375, 756-767; mpidig_rma_callbacks.c:806-820).  The target
+ * is in the inout role and the origin in the in role: the target's bits are
+ * those MPIX_Reduce_local_async(origin, target, ...) leaves.
+ *
+ * Padded pair types (DOUBLE_INT, LONG_INT, SHORT_INT, LONG_DOUBLE_INT): the
+ * result receives the data fields only and keeps its own padding bytes, as
+ * MPIR_Localcopy does; the target keeps its padding as in the reduction.
+ * MPI_NO_OP: result = target, the target is neither combined nor written and
+ * `origin` is not read (it may be NULL).  MPI_REPLACE: result = old target,
+ * target = origin.  MPIX_EQUAL is refused (MPI_ERR_OP).
+ *
+ * Errors are those of the reduction's entries, all decided before any device
+ * work: count < 0, a non-builtin op, an unknown type, an illegal (op, type),
+ * NULL buffers, a span of 2^56 bytes or more; any overlap among the three byte
+ * ranges is MPI_ERR_BUFFER; a legal pair without a kernel (bf16 other than
+ * SUM) is MPI_ERR_TYPE and touches no buffer.  count == 0 succeeds without
+ * looking at any pointer.
+ *
+ * The async forms take operands a kernel on `stream` can dereference (device
+ * memory, page-locked host memory; pageable host memory is MPI_ERR_BUFFER)
+ * and return without waiting.  The sync forms need a device-memory target, run
+ * on the calling thread's library stream and return when the result and the
+ * target are visible.
+ *
+ * Vector form: the target is MPI_Type_vector(count, blocklen, stride,
+ * basic_type) as in MPIX_Reduce_local_vector_async, origin and result are
+ * packed: for b < count, j < blocklen
+ *     result[b*blocklen + j] = target[b*stride + j]
+ *     target[b*stride + j]   = target[b*stride + j] OP origin[b*blocklen + j]
+ * Gap elements of the target are neither loaded nor written; the target's
+ * byte range for the overlap check is its span. */
+int MPIX_Get_accumulate_local_async(const void *origin, void *result, void *target,
+                                    MPIX_Aint count, MPIX_Datatype datatype, MPIX_Op op,
+                                    void *stream);
+int MPIX_Get_accumulate_local(const void *origin, void *result, void *target,
+                              MPIX_Aint count, MPIX_Datatype datatype, MPIX_Op op);
+int MPIX_Get_accumulate_local_vector_async(const void *origin, void *result, void *target,
+                                           MPIX_Aint count, MPIX_Aint blocklen, MPIX_Aint stride,
+                                           MPIX_Datatype basic_type, MPIX_Op op, void *stream);
+int MPIX_Get_accumulate_local_vector(const void *origin, void *result, void *target,
+                                     MPIX_Aint count, MPIX_Aint blocklen, MPIX_Aint stride,
+                                     MPIX_Datatype basic_type, MPIX_Op op);
 
 /* General derived target given as its flattened iov, packed source --
  * typerep_op_fallback (typerep_op.c:100-150) with the target's iov already

@@ -4,8 +4,8 @@
 // (src/mpi/coll/reduce_local/reduce_local.c:53-96): handle decoding,
 // (op, datatype) legality, pointer classification, the per-thread stream,
 // host-buffer staging, and the dispatch to the gfx950 kernels instantiated in
-// inst_{int,fp,pair}.hip.  There is no CPU compute path here: a combination
-// the GPU path does not cover returns MPIX_REDOP_ERR_TYPE and
+// inst_{int,fp,pair}.hip and inst_getacc_*.hip.  There is no CPU compute path
+// here: a combination the GPU path does not cover returns MPIX_REDOP_ERR_TYPE and
 // MPIX_Redop_is_supported() says so, so the caller keeps its own op table
 // for it (exactly how reduce_local.c:66-76 falls back when yaksa declines).
 #include <hip/hip_runtime_api.h>
@@ -237,6 +237,18 @@ const Entry *gpu_entry(uint32_t opi, uint32_t it)
         e = mpix::lookup_int((int) raw, (int) opi);
     if (!e)
         e = mpix::lookup_pair((int) raw, (int) opi);
+    return e;
+}
+
+// the fused get-accumulate's launchers of the same pair
+const mpix::GetaccEntry *getacc_entry(uint32_t opi, uint32_t it)
+{
+    uint32_t raw = is_struct_pair(it) ? it : (it & 0xffffff00u);
+    const mpix::GetaccEntry *e = mpix::lookup_getacc_fp((int) raw, (int) opi);
+    if (!e)
+        e = mpix::lookup_getacc_int((int) raw, (int) opi);
+    if (!e)
+        e = mpix::lookup_getacc_pair((int) raw, (int) opi);
     return e;
 }
 
@@ -2167,6 +2179,175 @@ int MPIX_Reduce_local_vector(const void *inbuf, void *inoutbuf, MPIX_Aint count,
                                             op, d->s[0]);
     int rc2 = wait_stream(d, d->s[0]);
     return set_err(rc ? rc : rc2);
+}
+
+// ------------------------------------------------ fused get-accumulate
+// One implementation for both forms: the contiguous one is the vector target
+// with blocklen = stride = 1.
+static bool ranges_overlap(const void *a, uint64_t na, const void *b, uint64_t nb)
+{
+    const uintptr_t x = (uintptr_t) a, y = (uintptr_t) b;
+    return x < y + nb && y < x + na;
+}
+
+static bool no_buffer(const void *p) { return !p || p == (const void *) -1; }
+
+// Every check that needs no device: on success *n holds the packed element
+// count (0: nothing to do, no pointer was looked at).
+static int getacc_validate(const void *origin, const void *result, const void *target,
+                           MPIX_Aint count, MPIX_Aint blocklen, MPIX_Aint stride, uint32_t dt,
+                           uint32_t op, uint32_t *it, uint64_t *ext, uint64_t *n)
+{
+    *n = 0;
+    if (count < 0 || blocklen < 0)
+        return MPIX_REDOP_ERR_COUNT;
+    if (stride < blocklen)
+        return MPIX_REDOP_ERR_ARG;      // overlapping target runs
+    if (is_builtin_op(op) && (op & 0xf) == 15)
+        return MPIX_REDOP_ERR_OP;       // MPIX_EQUAL is no accumulate op
+    int rc = validate(nullptr, nullptr, 0, dt, op, it, ext);
+    if (rc != MPIX_REDOP_SUCCESS || count == 0 || blocklen == 0)
+        return rc;
+    // no operand spans 2^56 bytes (validate's cap), the target's span included
+    const uint64_t cap = ((uint64_t) 1 << 56) / *ext;
+    const uint64_t c = (uint64_t) count, bl = (uint64_t) blocklen, st = (uint64_t) stride;
+    if (bl > cap || c > cap / bl || (c > 1 && st > (cap - bl) / (c - 1)))
+        return MPIX_REDOP_ERR_COUNT;
+    const uint32_t opi = op & 0xf;
+    const bool reads_origin = opi != 14;    // MPI_NO_OP: origin may be NULL
+    if (no_buffer(result) || no_buffer(target) || (reads_origin && no_buffer(origin)))
+        return MPIX_REDOP_ERR_BUFFER;
+    const uint64_t packed = c * bl * *ext, span = ((c - 1) * st + bl) * *ext;
+    if (ranges_overlap(result, packed, target, span) ||
+        (reads_origin && (ranges_overlap(origin, packed, target, span) ||
+                          ranges_overlap(origin, packed, result, packed))))
+        return MPIX_REDOP_ERR_BUFFER;
+    if (opi < 13 && !getacc_entry(opi, *it))
+        return MPIX_REDOP_ERR_TYPE;     // a legal pair without a kernel
+    *n = c * bl;
+    return MPIX_REDOP_SUCCESS;
+}
+
+// Type-map copy (MPIR_Localcopy) of `count` blocks of `bl` elements between
+// two buffers whose blocks start every dp / sp elements.
+static int copy_blocks(void *dst, uint64_t dp, const void *src, uint64_t sp, uint64_t count,
+                       uint64_t bl, uint32_t it, uint64_t ext, hipStream_t s)
+{
+    if (dp == bl && sp == bl)
+        return replace_rows(dst, ext, src, ext, count * bl, it, ext, s);
+    PairMap pm;
+    if (!padded_pair(it, &pm))
+        return hip_err(hipMemcpy2DAsync(dst, dp * ext, src, sp * ext, bl * ext, count,
+                                        hipMemcpyDeviceToDevice, s));
+    int rc = MPIX_REDOP_SUCCESS;
+    if (bl <= count) {      // column k of every block
+        for (uint64_t k = 0; k < bl && rc == MPIX_REDOP_SUCCESS; ++k)
+            rc = replace_rows((char *) dst + k * ext, dp * ext, (const char *) src + k * ext,
+                              sp * ext, count, it, ext, s);
+    } else {                // block by block
+        for (uint64_t b = 0; b < count && rc == MPIX_REDOP_SUCCESS; ++b)
+            rc = replace_rows((char *) dst + b * dp * ext, ext, (const char *) src + b * sp * ext,
+                              ext, bl, it, ext, s);
+    }
+    return rc;
+}
+
+// Validated arguments: operand placement, then the launch on `s`.  NO_OP and
+// REPLACE are the stream-ordered copies (fetch, then replace); every other op
+// is one fused kernel.
+static int getacc_enqueue(const void *origin, void *result, void *target, uint64_t count,
+                          uint64_t bl, uint64_t st, uint32_t it, uint64_t ext, uint32_t op,
+                          hipStream_t s)
+{
+    const uint32_t opi = op & 0xf;
+    const void *po = origin, *pr, *pt;
+    int launch = -2;
+    bool zc = false;
+    if (!reachable(result, s, &launch, &pr, &zc) || !reachable(target, s, &launch, &pt, &zc) ||
+        (opi != 14 && !reachable(origin, s, &launch, &po, &zc)))
+        return MPIX_REDOP_ERR_BUFFER;
+    if (opi == 13 || opi == 14) {
+        int rc = copy_blocks((void *) pr, bl, pt, st, count, bl, it, ext, s);
+        if (rc == MPIX_REDOP_SUCCESS && opi == 13)
+            rc = copy_blocks((void *) pt, st, po, bl, count, bl, it, ext, s);
+        return rc;
+    }
+    const mpix::GetaccEntry *e = getacc_entry(opi, it);
+    if (!e)
+        return MPIX_REDOP_ERR_TYPE;
+    if (bl == st)
+        return hip_err(e->contig(po, (void *) pr, (void *) pt, count * bl, params(),
+                                 launch_cfg(zc), s));
+    return hip_err(e->vector(po, (void *) pr, (void *) pt, count, bl, st, params(), launch_cfg(),
+                             s));
+}
+
+static int getacc_async(const void *origin, void *result, void *target, MPIX_Aint count,
+                        MPIX_Aint blocklen, MPIX_Aint stride, uint32_t dt, uint32_t op,
+                        hipStream_t s)
+{
+    uint32_t it;
+    uint64_t ext, n;
+    int rc = getacc_validate(origin, result, target, count, blocklen, stride, dt, op, &it, &ext, &n);
+    if (rc != MPIX_REDOP_SUCCESS || n == 0)
+        return rc;
+    return getacc_enqueue(origin, result, target, (uint64_t) count, (uint64_t) blocklen,
+                          (uint64_t) stride, it, ext, op, s);
+}
+
+// the synchronous forms: a device-memory target, the calling thread's library
+// stream of that device, and a wait on it (no in-kernel completion word)
+static int getacc_sync(const void *origin, void *result, void *target, MPIX_Aint count,
+                       MPIX_Aint blocklen, MPIX_Aint stride, uint32_t dt, uint32_t op)
+{
+    uint32_t it;
+    uint64_t ext, n;
+    int rc = getacc_validate(origin, result, target, count, blocklen, stride, dt, op, &it, &ext, &n);
+    if (rc != MPIX_REDOP_SUCCESS || n == 0)
+        return rc;
+    int dev = 0;
+    const void *dp;
+    if (classify(target, &dev, &dp) != Where::Device)
+        return MPIX_REDOP_ERR_BUFFER;
+    DeviceGuard guard(dev);
+    DevState *d = dev_state(dev);
+    if (!d)
+        return MPIX_REDOP_ERR_OTHER;
+    rc = getacc_enqueue(origin, result, target, (uint64_t) count, (uint64_t) blocklen,
+                        (uint64_t) stride, it, ext, op, d->s[0]);
+    const int rc2 = wait_stream(d, d->s[0]);
+    return rc ? rc : rc2;
+}
+
+int MPIX_Get_accumulate_local_async(const void *origin, void *result, void *target,
+                                    MPIX_Aint count, MPIX_Datatype datatype, MPIX_Op op,
+                                    void *stream)
+{
+    return set_err(getacc_async(origin, result, target, count, 1, 1, (uint32_t) datatype,
+                                (uint32_t) op, (hipStream_t) stream));
+}
+
+int MPIX_Get_accumulate_local(const void *origin, void *result, void *target, MPIX_Aint count,
+                              MPIX_Datatype datatype, MPIX_Op op)
+{
+    return set_err(getacc_sync(origin, result, target, count, 1, 1, (uint32_t) datatype,
+                               (uint32_t) op));
+}
+
+int MPIX_Get_accumulate_local_vector_async(const void *origin, void *result, void *target,
+                                           MPIX_Aint count, MPIX_Aint blocklen, MPIX_Aint stride,
+                                           MPIX_Datatype basic_type, MPIX_Op op, void *stream)
+{
+    return set_err(getacc_async(origin, result, target, count, blocklen, stride,
+                                (uint32_t) basic_type, (uint32_t) op, (hipStream_t) stream));
+}
+
+int MPIX_Get_accumulate_local_vector(const void *origin, void *result, void *target,
+                                     MPIX_Aint count, MPIX_Aint blocklen, MPIX_Aint stride,
+                                     MPIX_Datatype basic_type, MPIX_Op op)
+{
+    return set_err(getacc_sync(origin, result, target, count, blocklen, stride,
+                               (uint32_t) basic_type, (uint32_t) op));
 }
 
 int MPIX_Reduce_local_iov_async(const void *inbuf, void *inoutbuf, MPIX_Aint nseg,

@@ -93,6 +93,22 @@ const Entry *lookup_int(int raw, int opi);
 const Entry *lookup_fp(int raw, int opi);
 const Entry *lookup_pair(int raw, int opi);
 
+// The fused get-accumulate (MPIX_Get_accumulate_local*): result = target,
+// target = target OP origin in one pass.  A table of its own, built in its own
+// instantiation units (inst_getacc_*.hip) so they compile beside the
+// reduction's; a pair has a GetaccEntry exactly when it has an Entry.
+struct GetaccEntry {
+    hipError_t (*contig)(const void *origin, void *result, void *target, uint64_t count,
+                         const Params &, const LaunchCfg &, hipStream_t);
+    hipError_t (*vector)(const void *origin, void *result, void *target, uint64_t count,
+                         uint64_t blocklen, uint64_t stride, const Params &, const LaunchCfg &,
+                         hipStream_t);
+};
+
+const GetaccEntry *lookup_getacc_int(int raw, int opi);
+const GetaccEntry *lookup_getacc_fp(int raw, int opi);
+const GetaccEntry *lookup_getacc_pair(int raw, int opi);
+
 // MPIX_EQUAL on an MPI_BYTE buffer of n >= 8 bytes (opequal.c:20-35)
 hipError_t launch_equal(const void *in, void *io, uint64_t n, hipStream_t s);
 

@@ -1401,6 +1401,220 @@ hipError_t launch_batch(const void *const *ins, void *const *ios, const uint64_t
     }
 }
 
+// ---------------------------------------------------------------------------
+// Fused get-accumulate (MPIX_Get_accumulate_local*): result = target as it
+// was, target = target OP origin, the target read once -- 4 x bytes where the
+// reference's copy followed by the op (posix_rma.h:366-375) moves 5 x.  The
+// combiners are the reduction's own, with the target in the inout role, so the
+// target's bits are those of the reduce entry.  No shared state: the split
+// combiners run their full C::apply element-wise and never touch the fixup
+// words.
+
+// The result takes the type map only (MPIR_Localcopy): the struct pairs with
+// padding get their value and their int stored member by member, so the
+// result's own padding bytes stay as they were.
+template <class T> struct FetchStore {
+    static __device__ __forceinline__ void st(T *dst, const T &v) { *dst = v; }
+    static constexpr bool whole = true;
+};
+#define MPIX_FETCH_MEMBERS(T)                                                  \
+    template <> struct FetchStore<T> {                                         \
+        static __device__ __forceinline__ void st(T *dst, const T &v)          \
+        {                                                                      \
+            dst->v = v.v;                                                      \
+            dst->l = v.l;                                                      \
+        }                                                                      \
+        static constexpr bool whole = false;                                   \
+    }
+MPIX_FETCH_MEMBERS(DoubleIntBody);
+MPIX_FETCH_MEMBERS(LongIntBody);
+MPIX_FETCH_MEMBERS(ShortInt);
+MPIX_FETCH_MEMBERS(LongDoubleInt);     // the long double's 16 bytes and the int
+#undef MPIX_FETCH_MEMBERS
+
+// Cache policy of the packet store to `result`, a line written once and not
+// read again by this call: 0 non-temporal, 1 plain, 2 write-through, 3 the
+// policy of the block's target store (st16_pol).  The choice is measured
+// (tools/getacc_rows.py, DESIGN.md "Fused get-accumulate").
+#ifndef MPIX_GETACC_RESULT_STORE
+#define MPIX_GETACC_RESULT_STORE 0
+#endif
+
+// 16-byte store to `result`; !ALN: the address is only element-aligned
+// (ld16u's counterpart, still one global_store_dwordx4)
+typedef v4u v4u_unaligned __attribute__((aligned(1)));
+template <bool ALN, int POL> __device__ __forceinline__ void st16_result(char *p, v4u v, bool wt)
+{
+    using V = std::conditional_t<ALN, v4u, v4u_unaligned>;
+    typedef __attribute__((address_space(1))) V gV;
+    V *q = reinterpret_cast<V *>(p);
+    if (POL == 2 || (POL == 3 && wt))
+        *(volatile gV *) (gV *) q = v;
+    else if constexpr (POL == 1)
+        *q = v;
+    else
+        __builtin_nontemporal_store(v, q);
+}
+
+// Packet kernel, units of at most 16 bytes, all three operands element-aligned:
+// contig_body's head / packets / tail split by the target's 16-byte phase, one
+// packet per lane.  ALN: origin and result share that phase (packet accesses);
+// otherwise either is only element-aligned and both go through unaligned
+// 16-byte accesses.  Both loads are issued before the combine.
+template <class C, bool NTL, bool NTS, bool ALN>
+__global__ void __launch_bounds__(1024)
+k_getacc(const typename C::unit *__restrict__ in, typename C::unit *__restrict__ res,
+         typename C::unit *__restrict__ io, uint64_t head, uint64_t npk, uint64_t tail_start,
+         uint32_t ntail, Params prm, uint32_t nblk, uint32_t nt)
+{
+    using T = typename C::unit;
+    constexpr int E = 16 / sizeof(T);
+    const v4u *__restrict__ vin = reinterpret_cast<const v4u *>(in + head);
+    const char *__restrict__ cin = reinterpret_cast<const char *>(in + head);
+    char *__restrict__ cres = reinterpret_cast<char *>(res + head);
+    v4u *__restrict__ vio = reinterpret_cast<v4u *>(io + head);
+    const uint64_t stride = (uint64_t) nblk * nt;
+    const bool wt = wt_block(prm);
+    for (uint64_t i = (uint64_t) blockIdx.x * nt + threadIdx.x; i < npk; i += stride) {
+        const v4u a = ld16<NTL>(vio + i);
+        v4u b;
+        if constexpr (ALN)
+            b = ld16<NTL>(vin + i);
+        else
+            b = ld16u(cin + 16 * i);
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (FetchStore<T>::whole) {
+            st16_result<ALN, MPIX_GETACC_RESULT_STORE>(cres + 16 * i, a, wt);
+        } else {
+            struct alignas(16) Pk { T u[E]; };
+            const Pk pa = __builtin_bit_cast(Pk, a);
+#pragma unroll
+            for (int e = 0; e < E; ++e)
+                FetchStore<T>::st(res + head + i * E + e, pa.u[e]);
+        }
+        st16_pol<NTS>(vio + i, combine16<C>(a, b, prm), wt);
+    }
+    if (blockIdx.x == 0) {
+        auto one = [&](uint64_t t) {
+            const T a = io[t];
+            FetchStore<T>::st(res + t, a);
+            io[t] = C::apply(a, in[t], prm);
+        };
+        for (uint64_t t = threadIdx.x; t < head; t += nt)
+            one(t);
+        for (uint64_t t = threadIdx.x; t < ntail; t += nt)
+            one(tail_start + t);
+    }
+}
+
+// Element-wise: operands that are not element-aligned, and every 32-byte unit
+// (the x87 / binary128 pairs and complex types; a split combiner's full apply)
+template <class C>
+__global__ void __launch_bounds__(1024)
+k_getacc_elem(const typename C::unit *__restrict__ in, typename C::unit *__restrict__ res,
+              typename C::unit *__restrict__ io, uint64_t n, Params prm, uint32_t nblk, uint32_t nt)
+{
+    using T = typename C::unit;
+    const uint64_t stride = (uint64_t) nblk * nt;
+    for (uint64_t i = (uint64_t) blockIdx.x * nt + threadIdx.x; i < n; i += stride) {
+        const T a = io[i];
+        FetchStore<T>::st(res + i, a);
+        io[i] = C::apply(a, in[i], prm);
+    }
+}
+
+// Vector target (MPI_Type_vector(count, bl, st)), origin and result packed:
+// packed element j = b*bl + k pairs with target element b*st + k; gap elements
+// are neither loaded nor stored.
+template <class C>
+__global__ void __launch_bounds__(1024)
+k_getacc_vector(const typename C::unit *__restrict__ in, typename C::unit *__restrict__ res,
+                typename C::unit *__restrict__ io, uint64_t n, uint64_t bl, uint64_t st, Params prm,
+                uint32_t nblk, uint32_t nt)
+{
+    using T = typename C::unit;
+    const uint64_t stride = (uint64_t) nblk * nt;
+    for (uint64_t j = (uint64_t) blockIdx.x * nt + threadIdx.x; j < n; j += stride) {
+        uint64_t t = j * st;
+        if (bl != 1) {      // uniform
+            const uint64_t b = j / bl;
+            t = b * st + (j - b * bl);
+        }
+        const T a = io[t];
+        FetchStore<T>::st(res + j, a);
+        io[t] = C::apply(a, in[j], prm);
+    }
+}
+
+template <class C>
+hipError_t launch_getacc(const void *in, void *res, void *io, uint64_t count, const Params &prm,
+                         const LaunchCfg &cfg, hipStream_t s)
+{
+    using T = typename C::unit;
+    const T *tin = static_cast<const T *>(in);
+    T *tres = static_cast<T *>(res), *tio = static_cast<T *>(io);
+    const uintptr_t ai = reinterpret_cast<uintptr_t>(in), ar = reinterpret_cast<uintptr_t>(res),
+                    ao = reinterpret_cast<uintptr_t>(io);
+    Params p = prm;
+    p.done = nullptr;       // the fetch entries wait on the stream
+    p.fixup = nullptr;
+    bool packets = false;
+    if constexpr (sizeof(T) <= 16)
+        packets = (ai % sizeof(T)) == 0 && (ar % sizeof(T)) == 0 && (ao % sizeof(T)) == 0;
+    if (packets) {
+        if constexpr (sizeof(T) <= 16) {
+            constexpr uint64_t E = 16 / sizeof(T);
+            uint64_t head = ((16 - (ao & 15)) & 15) / sizeof(T);
+            if (head > count)
+                head = count;
+            const uint64_t npk = (count - head) / E;
+            const uint64_t tail_start = head + npk * E;
+            const uint32_t ntail = (uint32_t) (count - tail_start);
+            const unsigned grid = grid_for((uint64_t) cfg.block, npk, cfg.max_grid, cfg.block);
+            set_store_policy(p, cfg, grid);
+            if ((ai & 15) == (ao & 15) && (ar & 15) == (ao & 15))
+                hipLaunchKernelGGL((k_getacc<C, MPIX_REDOP_NT_LOAD, MPIX_REDOP_NT_STORE, true>),
+                                   dim3(grid), dim3(cfg.block), 0, s, tin, tres, tio, head, npk,
+                                   tail_start, ntail, p, grid, (uint32_t) cfg.block);
+            else
+                hipLaunchKernelGGL((k_getacc<C, MPIX_REDOP_NT_LOAD, MPIX_REDOP_NT_STORE, false>),
+                                   dim3(grid), dim3(cfg.block), 0, s, tin, tres, tio, head, npk,
+                                   tail_start, ntail, p, grid, (uint32_t) cfg.block);
+        }
+    } else {
+        const unsigned grid = grid_for((uint64_t) cfg.block * 4, count, cfg.max_grid, cfg.block);
+        hipLaunchKernelGGL((k_getacc_elem<C>), dim3(grid), dim3(cfg.block), 0, s, tin, tres, tio,
+                           count, p, grid, (uint32_t) cfg.block);
+    }
+    return hipGetLastError();
+}
+
+template <class C>
+hipError_t launch_getacc_vector(const void *in, void *res, void *io, uint64_t count, uint64_t bl,
+                                uint64_t st, const Params &prm, const LaunchCfg &cfg,
+                                hipStream_t s)
+{
+    using T = typename C::unit;
+    const uint64_t n = count * bl;
+    if (n == 0)
+        return hipSuccess;
+    if (bl == st)       // contiguous after all
+        return launch_getacc<C>(in, res, io, n, prm, cfg, s);
+    Params p = prm;
+    p.done = nullptr;
+    p.fixup = nullptr;
+    const unsigned grid = grid_for((uint64_t) cfg.block * 4, n, cfg.max_grid, cfg.block);
+    hipLaunchKernelGGL((k_getacc_vector<C>), dim3(grid), dim3(cfg.block), 0, s,
+                       static_cast<const T *>(in), static_cast<T *>(res), static_cast<T *>(io), n, bl,
+                       st, p, grid, (uint32_t) cfg.block);
+    return hipGetLastError();
+}
+
+template <class C> constexpr GetaccEntry getacc_entry()
+{
+    return GetaccEntry{&launch_getacc<C>, &launch_getacc_vector<C>};
+}
+
 template <class C> constexpr Entry entry()
 {
     return Entry{&launch_contig<C>, &launch_vector<C>, &launch_multi<C>, &launch_iov<C>,

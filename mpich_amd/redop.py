@@ -46,6 +46,11 @@ def lib():
             'MPIX_Reduce_local_async': ([vp, vp, aint, i32, i32, vp], i32),
             'MPIX_Reduce_local_vector': ([vp, vp, aint, aint, aint, i32, i32], i32),
             'MPIX_Reduce_local_vector_async': ([vp, vp, aint, aint, aint, i32, i32, vp], i32),
+            'MPIX_Get_accumulate_local': ([vp, vp, vp, aint, i32, i32], i32),
+            'MPIX_Get_accumulate_local_async': ([vp, vp, vp, aint, i32, i32, vp], i32),
+            'MPIX_Get_accumulate_local_vector': ([vp, vp, vp, aint, aint, aint, i32, i32], i32),
+            'MPIX_Get_accumulate_local_vector_async': ([vp, vp, vp, aint, aint, aint, i32, i32,
+                                                        vp], i32),
             'MPIX_Reduce_local_multi_async': ([ctypes.POINTER(vp), i32, vp, aint, i32, i32, vp],
                                               i32),
             'MPIX_Reduce_local_tree_async': ([ctypes.POINTER(vp), i32, vp, aint, i32, i32, vp],
@@ -174,7 +179,9 @@ def _bounds(buf):
         while getattr(root, 'base', None) is not None and hasattr(root.base, 'ctypes'):
             root = root.base
         import numpy as np
-        return np.byte_bounds(root)
+        if hasattr(np, 'byte_bounds'):
+            return np.byte_bounds(root)
+        return np.lib.array_utils.byte_bounds(root)     # NumPy 2 moved it
     return None
 
 
@@ -229,6 +236,36 @@ def reduce_local_vector(inbuf, inoutbuf, count, blocklen, stride, basic_type, op
     return lib().MPIX_Reduce_local_vector_async(_addr(inbuf), _addr(inoutbuf), count, blocklen,
                                                 stride, H.as_c_int(basic_type), H.as_c_int(op),
                                                 _stream_ptr(stream))
+
+
+def get_accumulate_local(origin, result, target, count, datatype, op, stream=None, sync=False):
+    """Fused get-accumulate: result = target as it was, target = target OP
+    origin, one stream-ordered pass (MPI_Get_accumulate / MPI_Fetch_and_op's
+    local step).  `origin` may be None for MPI_NO_OP."""
+    _span_check(count, datatype, op, result, target, *([] if origin is None else [origin]))
+    args = (_addr(origin), _addr(result), _addr(target), count, H.as_c_int(datatype),
+            H.as_c_int(op))
+    if sync:
+        return lib().MPIX_Get_accumulate_local(*args)
+    return lib().MPIX_Get_accumulate_local_async(*args, _stream_ptr(stream))
+
+
+def get_accumulate_local_vector(origin, result, target, count, blocklen, stride, basic_type, op,
+                                stream=None, sync=False):
+    """The same with the target an MPI_Type_vector(count, blocklen, stride);
+    origin and result are packed."""
+    ext = _checked_extent(op, basic_type)
+    if ext > 0 and isinstance(count, int) and isinstance(blocklen, int) and count > 0 \
+            and blocklen > 0 and isinstance(stride, int) and stride >= blocklen:
+        _range_check(target, 0, ((count - 1) * stride + blocklen) * ext, 'vector target')
+        _range_check(result, 0, count * blocklen * ext, 'packed result')
+        if origin is not None:
+            _range_check(origin, 0, count * blocklen * ext, 'packed origin')
+    args = (_addr(origin), _addr(result), _addr(target), count, blocklen, stride,
+            H.as_c_int(basic_type), H.as_c_int(op))
+    if sync:
+        return lib().MPIX_Get_accumulate_local_vector(*args)
+    return lib().MPIX_Get_accumulate_local_vector_async(*args, _stream_ptr(stream))
 
 
 def reduce_local_iov_async(inbuf, inoutbuf, seg_offsets, seg_counts, basic_type, op,

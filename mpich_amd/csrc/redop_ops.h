@@ -244,6 +244,16 @@ template <typename R> struct CSum {
 template <typename R> MPIX_DEV R cpsign(R mag, R sgn) { return __builtin_copysign(mag, sgn); }
 template <> MPIX_DEV float cpsign<float>(float mag, float sgn) { return __builtin_copysignf(mag, sgn); }
 
+// A NaN part of a complex product becomes the one positive quiet NaN.  Each
+// part adds two products; where both are NaN the hardware returns the first
+// source's sign and payload, and which term the compiler makes the first
+// source differs from kernel to kernel -- the multi-input and tree folds
+// would then differ from the back-to-back calls they stand for in the bits of
+// a NaN (tests/test_fold_edges_gpu.py found that on MPI_C_FLOAT_COMPLEX and
+// MPI_COMPLEX4).  NaN payloads of arithmetic results are unpinned against the
+// reference anyway (x86 and gfx950 pick different default NaNs).
+template <typename R> MPIX_DEV R one_nan(R x) { return __builtin_isnan(x) ? (R) __builtin_nanf("") : x; }
+
 template <typename R> struct CProdAnnexG {
     using unit = Cplx<R>;
     static MPIX_DEV unit apply(unit x, unit y, const Params &)
@@ -255,6 +265,8 @@ template <typename R> struct CProdAnnexG {
         z.im = ad + bc;
         if (__builtin_expect(__builtin_isnan(z.re) && __builtin_isnan(z.im), 0))
             z = recover(a, b, c, d, ac, bd, ad, bc, z);
+        z.re = one_nan(z.re);
+        z.im = one_nan(z.im);
         return z;
     }
     static MPIX_DEV unit recover(R a, R b, R c, R d, R ac, R bd, R ad, R bc, unit z)
@@ -299,7 +311,8 @@ template <typename R> struct CProdAnnexG {
 // The four products and the two sums as packed fp16 pairs (v_pk_mul_f16 /
 // v_pk_add_f16 with operand selects): (p1, p3) = (re, im) * y.re, (p2, p4) =
 // (im, re) * y.im, z = (p1 - p2, p3 + p4) -- each lane the same single
-// correctly rounded fp16 op as the scalar form, 3 VALU per element instead of 7.
+// correctly rounded fp16 op as the scalar form, 3 VALU per element instead of 7
+// (before one_nan's compare and select per part).
 typedef _Float16 h2v __attribute__((ext_vector_type(2)));
 struct CProdHalf {
     using unit = Cplx<_Float16>;
@@ -312,8 +325,8 @@ struct CProdHalf {
         const h2v sg = {(_Float16) -1, (_Float16) 1};
         const h2v z = a + b * sg;       // (p1 - p2, p3 + p4): * -1 is exact
         unit r;
-        r.re = z.x;
-        r.im = z.y;
+        r.re = one_nan(z.x);
+        r.im = one_nan(z.y);
         return r;
     }
 };

@@ -268,6 +268,77 @@ int MPIX_Reduce_local_iovec_async(const void *inbuf, void *inoutbuf, MPIX_Aint n
                                   const MPIX_Aint *iov_offsets, const MPIX_Aint *iov_lens,
                                   MPIX_Datatype basic_type, MPIX_Op op, void *stream);
 
+/* ---- fused get-accumulate on iov / iovec targets ----
+ * MPI_Get_accumulate, MPI_Fetch_and_op, MPI_Get (MPI_NO_OP) and the swap
+ * (MPI_REPLACE) on any derived target datatype: MPIR_Localcopy(target ->
+ * result) followed by the iov walk of the accumulate (posix_rma.h:366-375,
+ * typerep_op.c:100-150) as one stream-ordered step that reads each target
+ * element once.  The target is described exactly as inoutbuf is for
+ * MPIX_Reduce_local_iov_async / _iovec_async (byte offsets that may be
+ * negative, the same 4-byte / 2-byte residue rule, the iovec form's gather of
+ * typerep_op.c:117-148); origin and result are packed, in run order: for run s
+ * and k < its count, with p = the elements of earlier runs + k
+ *     result[p]                                  = target element at seg_offsets[s] + k*extent
+ *     target element at seg_offsets[s] + k*extent = that element OP origin[p]
+ * The target's bits are those MPIX_Reduce_local_iov[ec]_async(origin, target,
+ * ...) leaves.  The result takes the type map only: padded pairs are stored
+ * member by member, so the result keeps its own padding and the target its
+ * padding and gap bytes.  MPI_NO_OP fetches only (origin not read, may be
+ * NULL; the target is not written), MPI_REPLACE swaps, MPIX_EQUAL is
+ * MPI_ERR_OP.  Either is one launch per residue class however many runs.
+ *
+ * Errors, all decided before any device work (the run-table upload included),
+ * in this order: nseg < 0 (MPI_ERR_COUNT); NULL tables (MPI_ERR_BUFFER); a
+ * negative count or length (MPI_ERR_COUNT; the iovec form looks up the type
+ * first, MPI_ERR_TYPE); a basic type's segment holding a partial element
+ * (iovec, MPI_ERR_ARG); an unknown type (MPI_ERR_TYPE); a non-builtin op, an
+ * illegal (op, type) or MPIX_EQUAL (MPI_ERR_OP).  A total of zero elements
+ * then succeeds without looking at any of the three pointers.  Otherwise: NULL
+ * or MPI_IN_PLACE result / target, or origin unless the op is MPI_NO_OP
+ * (MPI_ERR_BUFFER); a misaligned residue (MPI_ERR_ARG); a packed range or the
+ * target's bounding range -- lowest run start to highest run end, zero-length
+ * runs aside -- of 2^56 bytes or more (MPI_ERR_COUNT); any overlap among the
+ * packed origin, the packed result and that bounding range (MPI_ERR_BUFFER); a
+ * legal pair without a kernel (bf16 other than SUM: MPI_ERR_TYPE, no buffer
+ * touched).  Last, an operand the stream's device cannot dereference is
+ * MPI_ERR_BUFFER.  Runs overlapping one another remain the caller's contract.
+ *
+ * Async forms only; the table upload shares the reduce form's two slots and
+ * synchronises on their events, so these calls cannot be captured in a graph. */
+int MPIX_Get_accumulate_local_iov_async(const void *origin, void *result, void *target,
+                                        MPIX_Aint nseg, const MPIX_Aint *seg_offsets,
+                                        const MPIX_Aint *seg_counts, MPIX_Datatype basic_type,
+                                        MPIX_Op op, void *stream);
+int MPIX_Get_accumulate_local_iovec_async(const void *origin, void *result, void *target,
+                                          MPIX_Aint nseg, const MPIX_Aint *iov_offsets,
+                                          const MPIX_Aint *iov_lens, MPIX_Datatype basic_type,
+                                          MPIX_Op op, void *stream);
+
+/* ---- compare-and-swap ----
+ * The local step of MPI_Compare_and_swap on one element (posix_rma.h:605-608,
+ * mpidig_rma_callbacks.c:1059-1068):
+ *     *result = *target;  if (*compare == *target) *target = *origin;
+ * compared as integers of the element's size.  Legal types are those of
+ * MPIR_Type_is_rma_atomic (rmatypeutil.c:18-30): MPIX_Datatype_internal(
+ * datatype) is one of MPIX_INT8..INT128, MPIX_UINT8..UINT128; anything else
+ * (floating types, pairs, Fortran logicals) is MPI_ERR_TYPE and touches no
+ * buffer.  NULL or MPI_IN_PLACE in any of the four pointers, result
+ * overlapping any of the other three, or target overlapping origin or compare
+ * is MPI_ERR_BUFFER; origin and compare may be the same address.  No operand
+ * needs any alignment.
+ *
+ * Stream-ordered like every other entry, by plain loads and stores: atomicity
+ * against other streams or processes is the window lock's business, as in the
+ * reference, which holds a mutex around these lines.  The async form takes
+ * operands a kernel on `stream` can dereference (pageable host memory is
+ * MPI_ERR_BUFFER); the sync form needs a device-memory target, runs on the
+ * calling thread's library stream and returns when result and target are
+ * visible. */
+int MPIX_Compare_and_swap_local_async(const void *origin, const void *compare, void *result,
+                                      void *target, MPIX_Datatype datatype, void *stream);
+int MPIX_Compare_and_swap_local(const void *origin, const void *compare, void *result,
+                                void *target, MPIX_Datatype datatype);
+
 /* Multi-input form: equivalent to `ninputs` MPIX_Reduce_local calls
  *   for k = 0 .. ninputs-1:  inoutbuf = inoutbuf OP inbufs[k]
  * in that order (same association, same bits) but done in one pass over

@@ -252,6 +252,18 @@ const mpix::GetaccEntry *getacc_entry(uint32_t opi, uint32_t it)
     return e;
 }
 
+// ... and of its iov-target form
+const mpix::GetaccIovEntry *getacc_iov_entry(uint32_t opi, uint32_t it)
+{
+    uint32_t raw = is_struct_pair(it) ? it : (it & 0xffffff00u);
+    const mpix::GetaccIovEntry *e = mpix::lookup_getacc_iov_fp((int) raw, (int) opi);
+    if (!e)
+        e = mpix::lookup_getacc_iov_int((int) raw, (int) opi);
+    if (!e)
+        e = mpix::lookup_getacc_iov_pair((int) raw, (int) opi);
+    return e;
+}
+
 // ---------------------------------------------------------------- state
 std::atomic<long long> g_ftrue{1}, g_ffalse{0};
 // One-wave (64-thread) blocks of one packet per lane (round 5): kernel-trace
@@ -1658,6 +1670,111 @@ struct Run {
     int64_t off, n;
 };
 
+// The runs of one call grouped by their offset modulo the extent (zero-length
+// runs dropped).  Group g indexes the target in whole elements from
+// target + resid[g]; its table [seg_off n][prefix n+1][src_off n] (n =
+// nrun[g]) starts at tab[base[g]]: element offset of each run, elements of the
+// group before it (prefix[n] = gtotal[g]), and its first element's index in
+// the packed operands, which follow the call's run order.  Host work only.
+struct RunTable {
+    std::vector<int64_t> resid, gtotal, tab;
+    std::vector<size_t> base, nrun;
+};
+
+void group_runs(const std::vector<Run> &runs, int64_t e, RunTable *rt)
+{
+    std::vector<std::vector<size_t>> groups;
+    for (size_t k = 0; k < runs.size(); ++k) {
+        if (runs[k].n == 0)
+            continue;
+        int64_t r = ((runs[k].off % e) + e) % e;
+        size_t g = 0;
+        while (g < rt->resid.size() && rt->resid[g] != r)
+            ++g;
+        if (g == rt->resid.size()) {
+            rt->resid.push_back(r);
+            groups.emplace_back();
+        }
+        groups[g].push_back(k);
+    }
+    std::vector<int64_t> src_of(runs.size());
+    {
+        int64_t src = 0;
+        for (size_t k = 0; k < runs.size(); ++k) {
+            src_of[k] = src;
+            src += runs[k].n;
+        }
+    }
+    size_t need = 0;
+    for (const auto &g : groups)
+        need += 3 * g.size() + 1;
+    rt->tab.resize(need);
+    rt->base.resize(groups.size());
+    rt->nrun.resize(groups.size());
+    rt->gtotal.resize(groups.size());
+    size_t at = 0;
+    for (size_t g = 0; g < groups.size(); ++g) {
+        const size_t n = groups[g].size();
+        rt->base[g] = at;
+        rt->nrun[g] = n;
+        int64_t pre = 0;
+        for (size_t q = 0; q < n; ++q) {
+            const Run &r = runs[groups[g][q]];
+            rt->tab[at + q] = (r.off - rt->resid[g]) / e;
+            rt->tab[at + n + q] = pre;
+            rt->tab[at + 2 * n + 1 + q] = src_of[groups[g][q]];
+            pre += r.n;
+        }
+        rt->tab[at + 2 * n] = pre;
+        rt->gtotal[g] = pre;
+        at += 3 * n + 1;
+    }
+}
+
+// Upload a run table on `s` through the next of the current device's two
+// slots, shared by the reduce and the fetch forms.  On success *slot holds the
+// device copy (tab) and the caller records slot->done on `s` after the launches
+// that read it; whenever *slot is set, also on an error, that record is owed.
+int upload_runs(const RunTable &rt, hipStream_t s, DevState::IovSlot **slot)
+{
+    const size_t need = rt.tab.size();
+    int dev = 0;
+    (void) hipGetDevice(&dev);
+    DevState *d = dev_state(dev);
+    if (!d)
+        return MPIX_REDOP_ERR_OTHER;
+    DevState::IovSlot &sl = d->iov[d->iov_next++ & 1];
+    if (!sl.done && hipEventCreateWithFlags(&sl.done, hipEventDisableTiming) != hipSuccess)
+        return MPIX_REDOP_ERR_OTHER;
+    // the slot's previous table may still be read by kernels queued on any
+    // stream (this thread may have used another one then): wait for them
+    int rc = hip_err(hipEventSynchronize(sl.done));
+    if (rc != MPIX_REDOP_SUCCESS)
+        return rc;
+    if (sl.cap < need) {
+        if (sl.tab)
+            (void) hipFree(sl.tab);
+        if (sl.host)
+            (void) hipHostFree(sl.host);
+        sl.tab = nullptr;
+        sl.host = nullptr;
+        sl.cap = 0;
+        if (hipMalloc((void **) &sl.tab, need * sizeof(int64_t)) != hipSuccess)
+            return MPIX_REDOP_ERR_OTHER;
+        if (hipHostMalloc((void **) &sl.host, need * sizeof(int64_t), hipHostMallocDefault) !=
+            hipSuccess)
+            return MPIX_REDOP_ERR_OTHER;
+        sl.cap = need;
+    }
+    // the table goes through the pinned copy, so the upload is a true async
+    // copy on s (no wait on the caller's stream); both copies are free for
+    // reuse once sl.done, recorded after the launches, has fired
+    *slot = &sl;
+    memcpy(sl.host, rt.tab.data(), need * sizeof(int64_t));
+    return hip_err(hipMemcpyAsync(sl.tab, sl.host, need * sizeof(int64_t), hipMemcpyHostToDevice,
+                                  s));
+}
+
 // Enqueue a list of runs on `s`.  Runs are split by their offset modulo the
 // extent so each launch indexes inout in whole elements from one base
 // (inout + residue); the source offset table keeps the packed source in the
@@ -1705,92 +1822,19 @@ int enqueue_runs(const void *inbuf, void *inoutbuf, const std::vector<Run> &runs
     const Entry *en = gpu_entry(opi, it);
     if (!en)
         return MPIX_REDOP_ERR_TYPE;
-    // group by residue; per group the table is [seg_off n][prefix n+1][src_off n]
-    std::vector<int64_t> resid;
-    std::vector<std::vector<size_t>> groups;
-    for (size_t k = 0; k < runs.size(); ++k) {
-        if (runs[k].n == 0)
-            continue;
-        int64_t r = ((runs[k].off % e) + e) % e;
-        size_t g = 0;
-        while (g < resid.size() && resid[g] != r)
-            ++g;
-        if (g == resid.size()) {
-            resid.push_back(r);
-            groups.emplace_back();
-        }
-        groups[g].push_back(k);
+    RunTable rt;
+    group_runs(runs, e, &rt);
+    DevState::IovSlot *sl = nullptr;
+    rc = upload_runs(rt, s, &sl);
+    for (size_t g = 0; g < rt.resid.size() && rc == MPIX_REDOP_SUCCESS; ++g) {
+        const int64_t n = (int64_t) rt.nrun[g];
+        const int64_t *t = sl->tab + rt.base[g];
+        rc = hip_err(en->iov(inbuf, (char *) inoutbuf + rt.resid[g], t, t + n, t + 2 * n + 1, n,
+                             (uint64_t) rt.gtotal[g], params(), launch_cfg(), s));
     }
-    std::vector<int64_t> src_of(runs.size());
-    {
-        int64_t src = 0;
-        for (size_t k = 0; k < runs.size(); ++k) {
-            src_of[k] = src;
-            src += runs[k].n;
-        }
-    }
-    size_t need = 0;
-    for (const auto &g : groups)
-        need += 3 * g.size() + 1;
-    std::vector<int64_t> tab(need);
-    std::vector<size_t> base(groups.size());
-    std::vector<int64_t> gtotal(groups.size());
-    size_t at = 0;
-    for (size_t g = 0; g < groups.size(); ++g) {
-        const size_t n = groups[g].size();
-        base[g] = at;
-        int64_t pre = 0;
-        for (size_t q = 0; q < n; ++q) {
-            const Run &r = runs[groups[g][q]];
-            tab[at + q] = (r.off - resid[g]) / e;
-            tab[at + n + q] = pre;
-            tab[at + 2 * n + 1 + q] = src_of[groups[g][q]];
-            pre += r.n;
-        }
-        tab[at + 2 * n] = pre;
-        gtotal[g] = pre;
-        at += 3 * n + 1;
-    }
-    int dev = 0;
-    (void) hipGetDevice(&dev);
-    DevState *d = dev_state(dev);
-    if (!d)
-        return MPIX_REDOP_ERR_OTHER;
-    DevState::IovSlot &sl = d->iov[d->iov_next++ & 1];
-    if (!sl.done && hipEventCreateWithFlags(&sl.done, hipEventDisableTiming) != hipSuccess)
-        return MPIX_REDOP_ERR_OTHER;
-    // the slot's previous table may still be read by kernels queued on any
-    // stream (this thread may have used another one then): wait for them
-    rc = hip_err(hipEventSynchronize(sl.done));
-    if (rc != MPIX_REDOP_SUCCESS)
+    if (!sl)
         return rc;
-    if (sl.cap < need) {
-        if (sl.tab)
-            (void) hipFree(sl.tab);
-        if (sl.host)
-            (void) hipHostFree(sl.host);
-        sl.tab = nullptr;
-        sl.host = nullptr;
-        sl.cap = 0;
-        if (hipMalloc((void **) &sl.tab, need * sizeof(int64_t)) != hipSuccess)
-            return MPIX_REDOP_ERR_OTHER;
-        if (hipHostMalloc((void **) &sl.host, need * sizeof(int64_t), hipHostMallocDefault) !=
-            hipSuccess)
-            return MPIX_REDOP_ERR_OTHER;
-        sl.cap = need;
-    }
-    // the table goes through the pinned copy, so the upload is a true async
-    // copy on s (no wait on the caller's stream); both copies are free for
-    // reuse once sl.done, recorded after the launches below, has fired
-    memcpy(sl.host, tab.data(), need * sizeof(int64_t));
-    rc = hip_err(hipMemcpyAsync(sl.tab, sl.host, need * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    for (size_t g = 0; g < groups.size() && rc == MPIX_REDOP_SUCCESS; ++g) {
-        const int64_t n = (int64_t) groups[g].size();
-        const int64_t *t = sl.tab + base[g];
-        rc = hip_err(en->iov(inbuf, (char *) inoutbuf + resid[g], t, t + n, t + 2 * n + 1, n,
-                             (uint64_t) gtotal[g], params(), launch_cfg(), s));
-    }
-    int rc2 = hip_err(hipEventRecord(sl.done, s));
+    int rc2 = hip_err(hipEventRecord(sl->done, s));
     return rc ? rc : rc2;
 }
 
@@ -2350,48 +2394,45 @@ int MPIX_Get_accumulate_local_vector(const void *origin, void *result, void *tar
                                (uint32_t) basic_type, (uint32_t) op));
 }
 
-int MPIX_Reduce_local_iov_async(const void *inbuf, void *inoutbuf, MPIX_Aint nseg,
-                                const MPIX_Aint *seg_offsets, const MPIX_Aint *seg_counts,
-                                MPIX_Datatype basic_type, MPIX_Op op, void *stream)
+// The element runs of the flattened-iov forms (seg_counts in elements).
+static int runs_from_iov(MPIX_Aint nseg, const MPIX_Aint *seg_offsets, const MPIX_Aint *seg_counts,
+                         std::vector<Run> *runs)
 {
     if (nseg < 0)
-        return set_err(MPIX_REDOP_ERR_COUNT);
+        return MPIX_REDOP_ERR_COUNT;
     if (nseg > 0 && (!seg_offsets || !seg_counts))
-        return set_err(MPIX_REDOP_ERR_BUFFER);
-    std::vector<Run> runs;
-    runs.reserve((size_t) nseg);
+        return MPIX_REDOP_ERR_BUFFER;
+    runs->reserve((size_t) nseg);
     for (MPIX_Aint s = 0; s < nseg; ++s) {
         if (seg_counts[s] < 0)
-            return set_err(MPIX_REDOP_ERR_COUNT);
-        runs.push_back(Run{seg_offsets[s], seg_counts[s]});
+            return MPIX_REDOP_ERR_COUNT;
+        runs->push_back(Run{seg_offsets[s], seg_counts[s]});
     }
-    return set_err(enqueue_runs(inbuf, inoutbuf, runs, (uint32_t) basic_type, (uint32_t) op,
-                                (hipStream_t) stream));
+    return MPIX_REDOP_SUCCESS;
 }
 
-int MPIX_Reduce_local_iovec_async(const void *inbuf, void *inoutbuf, MPIX_Aint nseg,
-                                  const MPIX_Aint *iov_offsets, const MPIX_Aint *iov_lens,
-                                  MPIX_Datatype basic_type, MPIX_Op op, void *stream)
+// The element runs of the raw-iovec forms (iov_lens in bytes).
+static int runs_from_iovec(MPIX_Aint nseg, const MPIX_Aint *iov_offsets, const MPIX_Aint *iov_lens,
+                           uint32_t basic_type, std::vector<Run> *runs)
 {
     if (nseg < 0)
-        return set_err(MPIX_REDOP_ERR_COUNT);
+        return MPIX_REDOP_ERR_COUNT;
     if (nseg > 0 && (!iov_offsets || !iov_lens))
-        return set_err(MPIX_REDOP_ERR_BUFFER);
-    uint32_t it = to_internal((uint32_t) basic_type);
+        return MPIX_REDOP_ERR_BUFFER;
+    uint32_t it = to_internal(basic_type);
     uint64_t ext = extent_of(it), size = size_of(it);
     if (it == kNull || ext == 0)
-        return set_err(MPIX_REDOP_ERR_TYPE);
+        return MPIX_REDOP_ERR_TYPE;
     // typerep_op.c:115-149: segments are gathered until they hold one
     // element's data (pairtypes split by their padding); each call covers
     // curr_len / size elements laid out at extent stride from target_ptr,
     // and a partial element left at the end of a segment starts the next one
     const bool pairtype = size < ext;
-    std::vector<Run> runs;
-    runs.reserve((size_t) nseg);
+    runs->reserve((size_t) nseg);
     MPIX_Aint curr = 0, target = 0;
     for (MPIX_Aint i = 0; i < nseg; ++i) {
         if (iov_lens[i] < 0)
-            return set_err(MPIX_REDOP_ERR_COUNT);
+            return MPIX_REDOP_ERR_COUNT;
         if (pairtype) {
             if (curr == 0)
                 target = iov_offsets[i];
@@ -2404,17 +2445,219 @@ int MPIX_Reduce_local_iovec_async(const void *inbuf, void *inoutbuf, MPIX_Aint n
         }
         MPIX_Aint n = curr / (MPIX_Aint) size;
         MPIX_Aint data = n * (MPIX_Aint) size;
-        runs.push_back(Run{target, n});
+        runs->push_back(Run{target, n});
         if (pairtype) {
             curr -= data;
             if (curr > 0)
                 target = iov_offsets[i] + (iov_lens[i] - curr);
         } else if (curr != data) {
-            return set_err(MPIX_REDOP_ERR_ARG);   // the reference's MPIR_Assert (:147)
+            return MPIX_REDOP_ERR_ARG;            // the reference's MPIR_Assert (:147)
         }
     }
+    return MPIX_REDOP_SUCCESS;
+}
+
+int MPIX_Reduce_local_iov_async(const void *inbuf, void *inoutbuf, MPIX_Aint nseg,
+                                const MPIX_Aint *seg_offsets, const MPIX_Aint *seg_counts,
+                                MPIX_Datatype basic_type, MPIX_Op op, void *stream)
+{
+    std::vector<Run> runs;
+    int rc = runs_from_iov(nseg, seg_offsets, seg_counts, &runs);
+    if (rc != MPIX_REDOP_SUCCESS)
+        return set_err(rc);
     return set_err(enqueue_runs(inbuf, inoutbuf, runs, (uint32_t) basic_type, (uint32_t) op,
                                 (hipStream_t) stream));
+}
+
+int MPIX_Reduce_local_iovec_async(const void *inbuf, void *inoutbuf, MPIX_Aint nseg,
+                                  const MPIX_Aint *iov_offsets, const MPIX_Aint *iov_lens,
+                                  MPIX_Datatype basic_type, MPIX_Op op, void *stream)
+{
+    std::vector<Run> runs;
+    int rc = runs_from_iovec(nseg, iov_offsets, iov_lens, (uint32_t) basic_type, &runs);
+    if (rc != MPIX_REDOP_SUCCESS)
+        return set_err(rc);
+    return set_err(enqueue_runs(inbuf, inoutbuf, runs, (uint32_t) basic_type, (uint32_t) op,
+                                (hipStream_t) stream));
+}
+
+// The fetch form over runs.  Every check that needs no device comes first, in
+// the reduce form's order where it has the check too; then operand placement,
+// and only then the table upload and the launches: one per residue group, the
+// copy kernel for MPI_NO_OP / MPI_REPLACE, the combiner's fused kernel else.
+static int getacc_runs(const void *origin, void *result, void *target,
+                       const std::vector<Run> &runs, uint32_t dt, uint32_t op, hipStream_t s)
+{
+    uint32_t it;
+    uint64_t ext;
+    int rc = validate(nullptr, nullptr, 0, dt, op, &it, &ext);
+    if (rc != MPIX_REDOP_SUCCESS)
+        return rc;
+    const uint32_t opi = op & 0xf;
+    if (opi == 15)
+        return MPIX_REDOP_ERR_OP;       // MPIX_EQUAL is no accumulate op
+    // total elements and the target's bounding byte range [lo, hi): lowest run
+    // start to highest run end, zero-length runs aside; `over` once a packed
+    // operand or that range would reach 2^56 bytes
+    const uint64_t cap = ((uint64_t) 1 << 56) / ext;
+    const __int128 span_cap = (__int128) 1 << 56;
+    uint64_t total = 0;
+    __int128 lo = 0, hi = 0;
+    bool over = false, any = false;
+    for (const Run &r : runs) {
+        if (r.n == 0)
+            continue;
+        if ((uint64_t) r.n > cap || total + (uint64_t) r.n > cap) {
+            over = true;
+            break;
+        }
+        total += (uint64_t) r.n;
+        const __int128 a = r.off, b = a + (__int128) ((uint64_t) r.n * ext);
+        if (!any || a < lo)
+            lo = a;
+        if (!any || b > hi)
+            hi = b;
+        any = true;
+    }
+    if (!over && total == 0)
+        return MPIX_REDOP_SUCCESS;
+    const bool reads_origin = opi != 14;    // MPI_NO_OP: origin may be NULL
+    if (no_buffer(result) || no_buffer(target) || (reads_origin && no_buffer(origin)))
+        return MPIX_REDOP_ERR_BUFFER;
+    const int64_t e = (int64_t) ext, align = e < 4 ? e : 4;
+    for (const Run &r : runs)
+        if ((((r.off % e) + e) % e) % align)
+            return MPIX_REDOP_ERR_ARG;
+    if (over || hi - lo >= span_cap || total * ext >= (uint64_t) span_cap)
+        return MPIX_REDOP_ERR_COUNT;
+    const uint64_t packed = total * ext, span = (uint64_t) (hi - lo);
+    const char *tlo = (const char *) target + (int64_t) lo;
+    if (ranges_overlap(result, packed, tlo, span) ||
+        (reads_origin && (ranges_overlap(origin, packed, tlo, span) ||
+                          ranges_overlap(origin, packed, result, packed))))
+        return MPIX_REDOP_ERR_BUFFER;
+    const mpix::GetaccIovEntry *en = nullptr;
+    if (opi < 13 && !(en = getacc_iov_entry(opi, it)))
+        return MPIX_REDOP_ERR_TYPE;     // a legal pair without a kernel
+    const void *po = origin, *pr, *pt;
+    int launch = -2;
+    if (!reachable(result, s, &launch, &pr) || !reachable(target, s, &launch, &pt) ||
+        (reads_origin && !reachable(origin, s, &launch, &po)))
+        return MPIX_REDOP_ERR_BUFFER;
+    PairMap pm{0, 0};
+    (void) padded_pair(it, &pm);
+    RunTable rt;
+    group_runs(runs, e, &rt);
+    DevState::IovSlot *sl = nullptr;
+    rc = upload_runs(rt, s, &sl);
+    for (size_t g = 0; g < rt.resid.size() && rc == MPIX_REDOP_SUCCESS; ++g) {
+        const int64_t n = (int64_t) rt.nrun[g];
+        const int64_t *t = sl->tab + rt.base[g];
+        void *tg = (char *) pt + rt.resid[g];
+        if (en)
+            rc = hip_err(en->iov(po, (void *) pr, tg, t, t + n, t + 2 * n + 1, n,
+                                 (uint64_t) rt.gtotal[g], params(), launch_cfg(), s));
+        else
+            rc = hip_err(mpix::launch_getacc_iov_copy(opi == 13, (uint32_t) ext, pm.value_bytes,
+                                                      pm.loc_off, po, (void *) pr, tg, t, t + n,
+                                                      t + 2 * n + 1, n, (uint64_t) rt.gtotal[g],
+                                                      launch_cfg(), s));
+    }
+    if (!sl)
+        return rc;
+    const int rc2 = hip_err(hipEventRecord(sl->done, s));
+    return rc ? rc : rc2;
+}
+
+int MPIX_Get_accumulate_local_iov_async(const void *origin, void *result, void *target,
+                                        MPIX_Aint nseg, const MPIX_Aint *seg_offsets,
+                                        const MPIX_Aint *seg_counts, MPIX_Datatype basic_type,
+                                        MPIX_Op op, void *stream)
+{
+    std::vector<Run> runs;
+    int rc = runs_from_iov(nseg, seg_offsets, seg_counts, &runs);
+    if (rc != MPIX_REDOP_SUCCESS)
+        return set_err(rc);
+    return set_err(getacc_runs(origin, result, target, runs, (uint32_t) basic_type, (uint32_t) op,
+                               (hipStream_t) stream));
+}
+
+int MPIX_Get_accumulate_local_iovec_async(const void *origin, void *result, void *target,
+                                          MPIX_Aint nseg, const MPIX_Aint *iov_offsets,
+                                          const MPIX_Aint *iov_lens, MPIX_Datatype basic_type,
+                                          MPIX_Op op, void *stream)
+{
+    std::vector<Run> runs;
+    int rc = runs_from_iovec(nseg, iov_offsets, iov_lens, (uint32_t) basic_type, &runs);
+    if (rc != MPIX_REDOP_SUCCESS)
+        return set_err(rc);
+    return set_err(getacc_runs(origin, result, target, runs, (uint32_t) basic_type, (uint32_t) op,
+                               (hipStream_t) stream));
+}
+
+// MPI_Compare_and_swap's local step.  MPIR_Type_is_rma_atomic
+// (rmatypeutil.c:18-30): the integer group of internal types only.
+static int cas_validate(const void *origin, const void *compare, const void *result,
+                        const void *target, uint32_t dt, uint32_t *size)
+{
+    const uint32_t it = to_internal(dt);
+    if (it == kNull || !is_builtin(it) || !(it & 0x800000u) || (it & 0x400000u))
+        return MPIX_REDOP_ERR_TYPE;
+    const uint32_t kind = it & 0x0f0000u;
+    const uint64_t ext = extent_of(it);
+    if ((kind != 0x010000u && kind != 0x020000u) ||
+        (ext != 1 && ext != 2 && ext != 4 && ext != 8 && ext != 16))
+        return MPIX_REDOP_ERR_TYPE;
+    if (no_buffer(origin) || no_buffer(compare) || no_buffer(result) || no_buffer(target))
+        return MPIX_REDOP_ERR_BUFFER;
+    // origin and compare are both only read: they may share an address
+    if (ranges_overlap(result, ext, origin, ext) || ranges_overlap(result, ext, compare, ext) ||
+        ranges_overlap(result, ext, target, ext) || ranges_overlap(target, ext, origin, ext) ||
+        ranges_overlap(target, ext, compare, ext))
+        return MPIX_REDOP_ERR_BUFFER;
+    *size = (uint32_t) ext;
+    return MPIX_REDOP_SUCCESS;
+}
+
+static int cas_enqueue(const void *origin, const void *compare, void *result, void *target,
+                       uint32_t size, hipStream_t s)
+{
+    const void *po, *pc, *pr, *pt;
+    int launch = -2;
+    if (!reachable(origin, s, &launch, &po) || !reachable(compare, s, &launch, &pc) ||
+        !reachable(result, s, &launch, &pr) || !reachable(target, s, &launch, &pt))
+        return MPIX_REDOP_ERR_BUFFER;
+    return hip_err(mpix::launch_cas(size, po, pc, (void *) pr, (void *) pt, s));
+}
+
+int MPIX_Compare_and_swap_local_async(const void *origin, const void *compare, void *result,
+                                      void *target, MPIX_Datatype datatype, void *stream)
+{
+    uint32_t size;
+    int rc = cas_validate(origin, compare, result, target, (uint32_t) datatype, &size);
+    if (rc != MPIX_REDOP_SUCCESS)
+        return set_err(rc);
+    return set_err(cas_enqueue(origin, compare, result, target, size, (hipStream_t) stream));
+}
+
+int MPIX_Compare_and_swap_local(const void *origin, const void *compare, void *result,
+                                void *target, MPIX_Datatype datatype)
+{
+    uint32_t size;
+    int rc = cas_validate(origin, compare, result, target, (uint32_t) datatype, &size);
+    if (rc != MPIX_REDOP_SUCCESS)
+        return set_err(rc);
+    int dev = 0;
+    const void *dp;
+    if (classify(target, &dev, &dp) != Where::Device)
+        return set_err(MPIX_REDOP_ERR_BUFFER);
+    DeviceGuard guard(dev);
+    DevState *d = dev_state(dev);
+    if (!d)
+        return set_err(MPIX_REDOP_ERR_OTHER);
+    rc = cas_enqueue(origin, compare, result, target, size, d->s[0]);
+    const int rc2 = wait_stream(d, d->s[0]);
+    return set_err(rc ? rc : rc2);
 }
 
 int MPIX_Reduce_local_multi_async(const void *const *inbufs, int ninputs, void *inoutbuf,

@@ -109,6 +109,38 @@ const GetaccEntry *lookup_getacc_int(int raw, int opi);
 const GetaccEntry *lookup_getacc_fp(int raw, int opi);
 const GetaccEntry *lookup_getacc_pair(int raw, int opi);
 
+// The fetch form over an iov target (MPIX_Get_accumulate_local_iov[ec]_async):
+// Entry::iov's run table with the packed result beside the packed origin, both
+// indexed by d_src_off.  A table and units of its own again
+// (inst_getacc_iov_*.hip); a pair has a GetaccIovEntry exactly when it has a
+// GetaccEntry.
+struct GetaccIovEntry {
+    hipError_t (*iov)(const void *origin, void *result, void *target, const int64_t *d_seg_off,
+                      const int64_t *d_prefix, const int64_t *d_src_off, int64_t nseg,
+                      uint64_t total, const Params &, const LaunchCfg &, hipStream_t);
+};
+
+const GetaccIovEntry *lookup_getacc_iov_int(int raw, int opi);
+const GetaccIovEntry *lookup_getacc_iov_fp(int raw, int opi);
+const GetaccIovEntry *lookup_getacc_iov_pair(int raw, int opi);
+
+// MPI_NO_OP (gather the runs into the packed result) and, `replace`,
+// MPI_REPLACE (then scatter the packed origin's type map over the runs) on the
+// same table, one launch: elements of `extent` bytes whose type map is the
+// whole extent (value_bytes == 0) or a value of value_bytes at 0 and an int at
+// loc_off (the padded pairs).  hipErrorInvalidValue for a layout without a
+// kernel.  inst_getacc_copy.hip.
+hipError_t launch_getacc_iov_copy(bool replace, uint32_t extent, uint32_t value_bytes,
+                                  uint32_t loc_off, const void *origin, void *result, void *target,
+                                  const int64_t *d_seg_off, const int64_t *d_prefix,
+                                  const int64_t *d_src_off, int64_t nseg, uint64_t total,
+                                  const LaunchCfg &, hipStream_t);
+
+// MPI_Compare_and_swap on one integer element of `size` bytes (1, 2, 4, 8,
+// 16): *result = *target; if (*target == *compare) *target = *origin.
+hipError_t launch_cas(uint32_t size, const void *origin, const void *compare, void *result,
+                      void *target, hipStream_t);
+
 // MPIX_EQUAL on an MPI_BYTE buffer of n >= 8 bytes (opequal.c:20-35)
 hipError_t launch_equal(const void *in, void *io, uint64_t n, hipStream_t s);
 

@@ -1615,6 +1615,167 @@ template <class C> constexpr GetaccEntry getacc_entry()
     return GetaccEntry{&launch_getacc<C>, &launch_getacc_vector<C>};
 }
 
+// ---------------------------------------------------------------------------
+// The fetch form over an iov target (MPIX_Get_accumulate_local_iov[ec]_async):
+// k_iov's run table, origin and result packed.  Launch-local packed index j
+// lies in run s = the last one with prefix[s] <= j; with k = j - prefix[s] the
+// target element is seg_off[s] + k and the packed element of BOTH origin and
+// result is src_off[s] + k (the call's run order, not this residue group's).
+
+// How a lane finds its run: 0 = a binary search per lane over the whole
+// prefix table (k_iov's); 1 = one wave-uniform search for the wave's first
+// index, which serves every lane when the wave's last index lies in the same
+// run, else the lanes search from that run on.  The choice is measured
+// (tools/getacc_rows.py iov, DESIGN.md "Fused get-accumulate").
+#ifndef MPIX_GETACC_IOV_LOOKUP
+#define MPIX_GETACC_IOV_LOOKUP 1
+#endif
+
+// last s in [lo, hi] with prefix[s] <= j
+__device__ __forceinline__ int64_t iov_search(const int64_t *__restrict__ prefix, int64_t lo,
+                                              int64_t hi, uint64_t j)
+{
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if ((uint64_t) prefix[mid] <= j)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    return lo;
+}
+
+// The run of packed index j < total = prefix[nseg].  Every caller runs
+// 256-thread blocks over j = block * 256 + thread + i * (nblk * 256), so the
+// active lanes of a wave hold consecutive indices from j & ~63.
+template <int LOOKUP>
+__device__ __forceinline__ int64_t iov_run(const int64_t *__restrict__ prefix, int64_t nseg,
+                                           uint64_t j, uint64_t total)
+{
+    if constexpr (LOOKUP == 0) {
+        return iov_search(prefix, 0, nseg - 1, j);
+    } else {
+        const uint64_t w = j & ~(uint64_t) 63;
+        const uint64_t first =
+            ((uint64_t) __builtin_amdgcn_readfirstlane((uint32_t) (w >> 32)) << 32) |
+            __builtin_amdgcn_readfirstlane((uint32_t) w);
+        const uint64_t last = first + 63 < total ? first + 63 : total - 1;
+        const int64_t s = iov_search(prefix, 0, nseg - 1, first);       // wave-uniform
+        if ((uint64_t) prefix[s + 1] > last)
+            return s;
+        return iov_search(prefix, s, nseg - 1, j);
+    }
+}
+
+// Thread per packed element: the old target element is loaded once, stored to
+// the result through FetchStore (type map only) and combined.  32-byte units
+// and the split combiners run their full C::apply, as in k_getacc_elem: no
+// fixup words, no shared state.
+template <class C>
+__global__ void __launch_bounds__(256)
+k_getacc_iov(const typename C::unit *__restrict__ in, typename C::unit *__restrict__ res,
+             typename C::unit *__restrict__ io, const int64_t *__restrict__ seg_off,
+             const int64_t *__restrict__ prefix, const int64_t *__restrict__ src_off, int64_t nseg,
+             uint64_t total, Params prm, uint32_t nblk)
+{
+    using T = typename C::unit;
+    const uint64_t stride = (uint64_t) nblk * 256;        // 256-thread blocks (launch_getacc_iov)
+    for (uint64_t j = (uint64_t) blockIdx.x * 256 + threadIdx.x; j < total; j += stride) {
+        const int64_t s = iov_run<MPIX_GETACC_IOV_LOOKUP>(prefix, nseg, j, total);
+        const int64_t k = (int64_t) (j - (uint64_t) prefix[s]);
+        const int64_t t = seg_off[s] + k, p = src_off[s] + k;
+        const T a = io[t];
+        FetchStore<T>::st(res + p, a);
+        io[t] = C::apply(a, in[p], prm);
+    }
+}
+
+// MPI_NO_OP and MPI_REPLACE over the same table, one launch per residue group
+// however many runs it has: gather the runs' type map into the packed result
+// and, REPLACE, scatter the origin's type map over them.  T is the unit's body
+// (a raw unit of its extent, or the padded pair), not a combiner.
+template <class T, bool REPLACE>
+__global__ void __launch_bounds__(256)
+k_getacc_iov_copy(const T *__restrict__ in, T *__restrict__ res, T *__restrict__ io,
+                  const int64_t *__restrict__ seg_off, const int64_t *__restrict__ prefix,
+                  const int64_t *__restrict__ src_off, int64_t nseg, uint64_t total, uint32_t nblk)
+{
+    const uint64_t stride = (uint64_t) nblk * 256;
+    for (uint64_t j = (uint64_t) blockIdx.x * 256 + threadIdx.x; j < total; j += stride) {
+        const int64_t s = iov_run<MPIX_GETACC_IOV_LOOKUP>(prefix, nseg, j, total);
+        const int64_t k = (int64_t) (j - (uint64_t) prefix[s]);
+        const int64_t t = seg_off[s] + k, p = src_off[s] + k;
+        const T a = io[t];
+        FetchStore<T>::st(res + p, a);
+        if constexpr (REPLACE) {
+            const T b = in[p];
+            FetchStore<T>::st(io + t, b);
+        }
+    }
+}
+
+template <class C>
+hipError_t launch_getacc_iov(const void *in, void *res, void *io, const int64_t *d_seg_off,
+                             const int64_t *d_prefix, const int64_t *d_src_off, int64_t nseg,
+                             uint64_t total, const Params &prm, const LaunchCfg &cfg, hipStream_t s)
+{
+    using T = typename C::unit;
+    if (total == 0 || nseg == 0)
+        return hipSuccess;
+    Params p = prm;
+    p.done = nullptr;
+    p.fixup = nullptr;
+    const unsigned grid = grid_for(256ull * 4, total, cfg.max_grid, 256);
+    hipLaunchKernelGGL((k_getacc_iov<C>), dim3(grid), dim3(256), 0, s, static_cast<const T *>(in),
+                       static_cast<T *>(res), static_cast<T *>(io), d_seg_off, d_prefix, d_src_off,
+                       nseg, total, p, grid);
+    return hipGetLastError();
+}
+
+template <class T>
+hipError_t launch_getacc_iov_copy_as(bool replace, const void *in, void *res, void *io,
+                                     const int64_t *d_seg_off, const int64_t *d_prefix,
+                                     const int64_t *d_src_off, int64_t nseg, uint64_t total,
+                                     const LaunchCfg &cfg, hipStream_t s)
+{
+    if (total == 0 || nseg == 0)
+        return hipSuccess;
+    const unsigned grid = grid_for(256ull * 4, total, cfg.max_grid, 256);
+    if (replace)
+        hipLaunchKernelGGL((k_getacc_iov_copy<T, true>), dim3(grid), dim3(256), 0, s,
+                           static_cast<const T *>(in), static_cast<T *>(res), static_cast<T *>(io),
+                           d_seg_off, d_prefix, d_src_off, nseg, total, grid);
+    else
+        hipLaunchKernelGGL((k_getacc_iov_copy<T, false>), dim3(grid), dim3(256), 0, s,
+                           static_cast<const T *>(in), static_cast<T *>(res), static_cast<T *>(io),
+                           d_seg_off, d_prefix, d_src_off, nseg, total, grid);
+    return hipGetLastError();
+}
+
+template <class C> constexpr GetaccIovEntry getacc_iov_entry()
+{
+    return GetaccIovEntry{&launch_getacc_iov<C>};
+}
+
+// ---------------------------------------------------------------------------
+// MPI_Compare_and_swap's local step on one element of 1, 2, 4, 8 or 16 bytes
+// (posix_rma.h:605-608): plain loads and stores, stream-ordered like every
+// other entry; the four addresses need no alignment.
+template <class U>
+__global__ void __launch_bounds__(64)
+k_cas(const void *origin, const void *compare, void *result, void *target)
+{
+    typedef U UU __attribute__((aligned(1)));
+    if (threadIdx.x != 0 || blockIdx.x != 0)
+        return;
+    const U t = *static_cast<const UU *>(target);
+    const U c = *static_cast<const UU *>(compare);
+    const U o = *static_cast<const UU *>(origin);
+    *static_cast<UU *>(result) = t;
+    if (t == c)
+        *static_cast<UU *>(target) = o;
+}
+
 template <class C> constexpr Entry entry()
 {
     return Entry{&launch_contig<C>, &launch_vector<C>, &launch_multi<C>, &launch_iov<C>,

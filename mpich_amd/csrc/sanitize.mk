@@ -19,7 +19,9 @@ ORACLE = ../../oracle/build
 HOSTFLAGS = -O1 -g -fno-omit-frame-pointer -std=c++17 -fPIC -Wall -D__HIP_PLATFORM_AMD__ \
             -I/opt/rocm/include -I../../include -I.
 KOBJS = build/inst_int.o build/inst_fp.o build/inst_pair.o \
-        build/inst_getacc_int.o build/inst_getacc_fp.o build/inst_getacc_pair.o
+        build/inst_getacc_int.o build/inst_getacc_fp.o build/inst_getacc_pair.o \
+        build/inst_getacc_iov_int.o build/inst_getacc_iov_fp.o build/inst_getacc_iov_pair.o \
+        build/inst_getacc_copy.o
 
 all: $(OUT)/coll_host_sanitize
 

@@ -61,6 +61,12 @@ def lib():
                                              ctypes.POINTER(aint), i32, i32, vp], i32),
             'MPIX_Reduce_local_iovec_async': ([vp, vp, aint, ctypes.POINTER(aint),
                                                ctypes.POINTER(aint), i32, i32, vp], i32),
+            'MPIX_Get_accumulate_local_iov_async': ([vp, vp, vp, aint, ctypes.POINTER(aint),
+                                                     ctypes.POINTER(aint), i32, i32, vp], i32),
+            'MPIX_Get_accumulate_local_iovec_async': ([vp, vp, vp, aint, ctypes.POINTER(aint),
+                                                       ctypes.POINTER(aint), i32, i32, vp], i32),
+            'MPIX_Compare_and_swap_local': ([vp, vp, vp, vp, i32], i32),
+            'MPIX_Compare_and_swap_local_async': ([vp, vp, vp, vp, i32, vp], i32),
             'MPIX_Redop_is_supported': ([i32, aint, i32], i32),
             'MPIX_Redop_is_supported_buffers': ([i32, aint, i32, vp, vp], i32),
             'MPIX_Redop_set_support': ([i32, aint, aint, aint], i32),
@@ -304,6 +310,70 @@ def reduce_local_iovec_async(inbuf, inoutbuf, iov_offsets, iov_lens, basic_type,
     return lib().MPIX_Reduce_local_iovec_async(_addr(inbuf), _addr(inoutbuf), n, offs, lens,
                                                H.as_c_int(basic_type), H.as_c_int(op),
                                                _stream_ptr(stream))
+
+
+def _fetch_ranges(origin, result, target, lo, hi, packed, what):
+    """the fetch forms' three operands against their buffers' bounds: the
+    target from its lowest to its highest run byte, origin (unless None) and
+    result over the packed bytes"""
+    _range_check(target, lo, hi, what + ' target')
+    _range_check(result, 0, packed, 'packed result')
+    if origin is not None:
+        _range_check(origin, 0, packed, 'packed origin')
+
+
+def get_accumulate_local_iov(origin, result, target, seg_offsets, seg_counts, basic_type, op,
+                             stream=None):
+    """Fused get-accumulate on a derived target given as its flattened iov
+    (byte offsets, element counts); origin and result are packed in run
+    order.  `origin` may be None for MPI_NO_OP.  Stream-ordered."""
+    n = len(seg_offsets)
+    ext = _checked_extent(op, basic_type)
+    if ext > 0 and n and all(c >= 0 for c in seg_counts):
+        live = [(o, c) for o, c in zip(seg_offsets, seg_counts) if c > 0]
+        if live:
+            _fetch_ranges(origin, result, target, min(o for o, _ in live),
+                          max(o + c * ext for o, c in live), sum(c for _, c in live) * ext, 'iov')
+    offs = (ctypes.c_ssize_t * n)(*seg_offsets)
+    cnts = (ctypes.c_ssize_t * n)(*seg_counts)
+    return lib().MPIX_Get_accumulate_local_iov_async(
+        _addr(origin), _addr(result), _addr(target), n, offs, cnts, H.as_c_int(basic_type),
+        H.as_c_int(op), _stream_ptr(stream))
+
+
+def get_accumulate_local_iovec(origin, result, target, iov_offsets, iov_lens, basic_type, op,
+                               stream=None):
+    """The same with the target given as its raw iov (byte offsets, byte
+    lengths), gathered into runs as reduce_local_iovec_async does."""
+    n = len(iov_offsets)
+    ext = _checked_extent(op, basic_type)
+    size = datatype_size(basic_type) if ext > 0 else 0
+    if ext > 0 and size > 0 and n and all(x >= 0 for x in iov_lens):
+        live = [(o, ln) for o, ln in zip(iov_offsets, iov_lens) if ln > 0]
+        if live:
+            packed = sum(ln for _, ln in live) // size
+            _fetch_ranges(origin, result, target, min(o for o, _ in live),
+                          max(o + ln for o, ln in live), packed * ext, 'iovec')
+    offs = (ctypes.c_ssize_t * n)(*iov_offsets)
+    lens = (ctypes.c_ssize_t * n)(*iov_lens)
+    return lib().MPIX_Get_accumulate_local_iovec_async(
+        _addr(origin), _addr(result), _addr(target), n, offs, lens, H.as_c_int(basic_type),
+        H.as_c_int(op), _stream_ptr(stream))
+
+
+def compare_and_swap_local(origin, compare, result, target, datatype, stream=None, sync=False):
+    """MPI_Compare_and_swap's local step on one integer element: result = the
+    target's value; target = origin where compare == target."""
+    ext = datatype_extent(datatype)
+    if ext > 0:
+        for b, what in ((origin, 'origin'), (compare, 'compare'), (result, 'result'),
+                        (target, 'target')):
+            if b is not None:
+                _range_check(b, 0, ext, what)
+    args = (_addr(origin), _addr(compare), _addr(result), _addr(target), H.as_c_int(datatype))
+    if sync:
+        return lib().MPIX_Compare_and_swap_local(*args)
+    return lib().MPIX_Compare_and_swap_local_async(*args, _stream_ptr(stream))
 
 
 def reduce_local_multi_async(inbufs, inoutbuf, count, datatype, op, stream=None):

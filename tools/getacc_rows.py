@@ -15,7 +15,25 @@ algorithmic bytes, (b) on 5 N s.  The vector row: target (blocklen, stride) =
 MPIX_Reduce_local_vector_async.  One JSON line.
 
 usage: getacc_rows.py LIBPATH LABEL   (run once per build to compare builds,
-e.g. the result-store policies: EXTRA_FLAGS=-DMPIX_GETACC_RESULT_STORE=n)"""
+e.g. the result-store policies: EXTRA_FLAGS=-DMPIX_GETACC_RESULT_STORE=n)
+
+       getacc_rows.py LIBPATH LABEL iov [ROWS]
+The iov-target rows (ROWS: letters of ABCD, default all), same method, the
+forms timed in turn:
+  A  fp64 SUM, 1,024 runs of 65,536 elements, gaps of a run's length (512 MiB
+     packed)
+  B  fp64 SUM, 131,072 runs of 512 elements (the same bytes, a 3 MiB table)
+  C  fp64 SUM, runs of 8 elements, 8 Mi elements in all
+  D  DOUBLE_INT MAXLOC, the raw iovec of a contiguous 32 Mi-element array
+     ({value, int} segments, one run per element)
+each as (fused) MPIX_Get_accumulate_local_iov[ec]_async, (two_launch) the
+MPI_NO_OP gather of the same entry followed by MPIX_Reduce_local_iov[ec]_async,
+(reduce) that reduce call alone, the kernel's floor at 3 of the fused form's 4
+N s bytes, and, row A only, (memcpy_per_run) one hipMemcpyAsync per run
+followed by the reduce call: what a caller had before these entries.  The
+events bracket whole calls, so the host's table building shows wherever it
+outlasts the kernels.  Compare builds by running once per build, e.g. the run
+lookup: EXTRA_FLAGS=-DMPIX_GETACC_IOV_LOOKUP=n."""
 import ctypes
 import json
 import os
@@ -102,6 +120,124 @@ ROWS = [('MPI_FLOAT', 'MPI_SUM', 'fp32'), ('MPI_DOUBLE', 'MPI_SUM', 'fp64'),
         ('MPI_DOUBLE_INT', 'MPI_MAXLOC', 'double_int'), ('MPI_COMPLEX32', 'MPI_PROD', 'binary128')]
 
 
+def timed_forms(forms, stream):
+    """per-call ms of every form, batch by batch in turn: {name: sorted list}"""
+    for f in forms.values():
+        f()
+    stream.synchronize()
+    out = {k: [] for k in forms}
+    for _ in range(BATCHES):
+        for k, f in forms.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for _ in range(REPS):
+                f()
+            e1.record(stream)
+            stream.synchronize()
+            out[k].append(e0.elapsed_time(e1) / REPS)
+    return {k: sorted(v) for k, v in out.items()}
+
+
+def iov_row(name, tn, on, nruns, packed_bytes, t):
+    med = {k: v[len(v) // 2] for k, v in t.items()}
+    r = dict(row=name, type=tn, op=on, runs=nruns, packed_bytes=packed_bytes)
+    for k, v in t.items():
+        r[k + '_ms'] = round(med[k], 4)
+        r[k + '_spread_ms'] = [round(v[0], 4), round(v[-1], 4)]
+    r['fused_TBs'] = round(4 * packed_bytes / (med['fused'] * 1e-3) / 1e12, 3)
+    r['ratio_to_two_launch'] = round(med['fused'] / med['two_launch'], 4)
+    r['ratio_to_reduce'] = round(med['fused'] / med['reduce'], 4)
+    spread = max(t['two_launch'][-1] - t['two_launch'][0], t['fused'][-1] - t['fused'][0])
+    r['wins'] = bool(med['fused'] < med['two_launch'] - spread)
+    return r
+
+
+def iov_main():
+    import numpy as np
+    which = sys.argv[4] if len(sys.argv) > 4 else 'ABCD'
+    iov_sig = [vp, vp, vp, aint, vp, vp, i32, i32, vp]
+    L.MPIX_Get_accumulate_local_iov_async.argtypes = iov_sig
+    L.MPIX_Get_accumulate_local_iovec_async.argtypes = iov_sig
+    L.MPIX_Reduce_local_iov_async.argtypes = iov_sig[1:]
+    L.MPIX_Reduce_local_iovec_async.argtypes = iov_sig[1:]
+    dev = torch.device('cuda', 0)
+    t8 = torch.empty(1 << 30, dtype=torch.uint8, device=dev)
+    o8, r8 = (torch.empty(1 << 29, dtype=torch.uint8, device=dev) for _ in range(2))
+    s = torch.cuda.current_stream()
+    sp = s.cuda_stream
+    tp, op_, rp = t8.data_ptr(), o8.data_ptr(), r8.data_ptr()
+    no_op = H.as_c_int(H.MPI_NO_OP)
+    rows = []
+    shapes = dict(A=(1024, 65536), B=(131072, 512), C=(1 << 20, 8))
+    for name in 'ABC':
+        if name not in which:
+            continue
+        nruns, n = shapes[name]
+        dt, op = H.as_c_int(H.MPI_DOUBLE), H.as_c_int(H.MPI_SUM)
+        offs = (np.arange(nruns, dtype=np.int64) * (2 * n * 8))
+        cnts = np.full(nruns, n, np.int64)
+        po, pc = offs.ctypes.data, cnts.ctypes.data
+        fill(t8, 'fp64', 0x5EED0B11)
+        fill(o8, 'fp64', 0x5EED0B12)
+        torch.cuda.synchronize()
+        forms = {}
+
+        def fused():
+            ok(L.MPIX_Get_accumulate_local_iov_async(op_, rp, tp, nruns, po, pc, dt, op, sp),
+               'MPIX_Get_accumulate_local_iov_async')
+
+        def reduce():
+            ok(L.MPIX_Reduce_local_iov_async(op_, tp, nruns, po, pc, dt, op, sp),
+               'MPIX_Reduce_local_iov_async')
+
+        def two_launch():
+            ok(L.MPIX_Get_accumulate_local_iov_async(None, rp, tp, nruns, po, pc, dt, no_op, sp),
+               'MPIX_Get_accumulate_local_iov_async NO_OP')
+            reduce()
+        forms.update(fused=fused, two_launch=two_launch, reduce=reduce)
+        if name == 'A':
+            def memcpy_per_run():
+                for k in range(nruns):
+                    ok(L.hipMemcpyAsync(rp + k * n * 8, tp + int(offs[k]), n * 8, D2D, sp),
+                       'hipMemcpyAsync')
+                reduce()
+            forms['memcpy_per_run'] = memcpy_per_run
+        rows.append(iov_row(name, 'MPI_DOUBLE', 'MPI_SUM', nruns, nruns * n * 8,
+                            timed_forms(forms, s)))
+    if 'D' in which:
+        n = 32 << 20
+        dt, op = H.as_c_int(H.MPI_DOUBLE_INT), H.as_c_int(H.MPI_MAXLOC)
+        offs = np.empty(2 * n, np.int64)
+        offs[0::2] = np.arange(n, dtype=np.int64) * 16
+        offs[1::2] = offs[0::2] + 8
+        lens = np.empty(2 * n, np.int64)
+        lens[0::2], lens[1::2] = 8, 4
+        po, pl = offs.ctypes.data, lens.ctypes.data
+        fill(t8[:n * 16], 'double_int', 0x5EED0B13)
+        fill(o8, 'double_int', 0x5EED0B14)
+        torch.cuda.synchronize()
+
+        def fused_d():
+            ok(L.MPIX_Get_accumulate_local_iovec_async(op_, rp, tp, 2 * n, po, pl, dt, op, sp),
+               'MPIX_Get_accumulate_local_iovec_async')
+
+        def reduce_d():
+            ok(L.MPIX_Reduce_local_iovec_async(op_, tp, 2 * n, po, pl, dt, op, sp),
+               'MPIX_Reduce_local_iovec_async')
+
+        def two_launch_d():
+            ok(L.MPIX_Get_accumulate_local_iovec_async(None, rp, tp, 2 * n, po, pl, dt, no_op, sp),
+               'MPIX_Get_accumulate_local_iovec_async NO_OP')
+            reduce_d()
+        rows.append(iov_row('D', 'MPI_DOUBLE_INT', 'MPI_MAXLOC', n, n * 16,
+                            timed_forms(dict(fused=fused_d, two_launch=two_launch_d,
+                                             reduce=reduce_d), s)))
+    L.MPIX_Redop_build_info.restype = ctypes.c_char_p
+    print(json.dumps(dict(label=sys.argv[2], lib=os.path.basename(sys.argv[1]),
+                          build=L.MPIX_Redop_build_info().decode(), batches=BATCHES, reps=REPS,
+                          rows=rows)))
+
+
 def main():
     nbytes = 1 << 30
     dev = torch.device('cuda', 0)
@@ -156,4 +292,7 @@ def main():
 
 
 if __name__ == '__main__':
-    main()
+    if len(sys.argv) > 3 and sys.argv[3] == 'iov':
+        iov_main()
+    else:
+        main()

@@ -314,6 +314,109 @@ int MPIX_Get_accumulate_local_iovec_async(const void *origin, void *result, void
                                           const MPIX_Aint *iov_lens, MPIX_Datatype basic_type,
                                           MPIX_Op op, void *stream);
 
+/* ---- committed iov plans ----
+ * What MPI_Type_commit is to a datatype: the run table of one (iov, basic type)
+ * built once and kept, where the _iov_async / _iovec_async entries above rebuild
+ * and upload it on every call.  A caller keeps one plan per (count, committed
+ * datatype) beside the datatype's own iov cache.
+ *
+ * MPIX_Iov_plan_create takes the tables of MPIX_Reduce_local_iov_async,
+ * MPIX_Iov_plan_create_iovec those of MPIX_Reduce_local_iovec_async (the
+ * padded pairs' gather of typerep_op.c:117-148 included); both read them before
+ * they return.  Host work only, no HIP call: a plan can be created, queried and
+ * freed on a machine without a GPU.  Runs are produced as by those entries;
+ * zero-length runs are dropped; consecutive runs in call order merge into one
+ * when run k+1 starts at offset[k] + count[k] * extent (their packed elements
+ * are consecutive by construction, so no result bit changes; runs adjacent in
+ * memory but not consecutive in call order stay apart); the merged runs are
+ * grouped by their offset modulo the extent, and each group gets one 32-bit
+ * index per 256 packed elements for the kernels' run lookup.
+ *
+ * Everything that depends only on the table and the type is decided here, in
+ * this order: nseg < 0, or above INT_MAX (the reference asserts,
+ * typerep_op.c:111) (MPI_ERR_COUNT); NULL tables (MPI_ERR_BUFFER); a negative
+ * count or length (MPI_ERR_COUNT; the iovec form looks up the type first,
+ * MPI_ERR_TYPE); a basic type's segment holding a partial element (iovec,
+ * MPI_ERR_ARG); an unknown type (MPI_ERR_TYPE); a residue off the 4-byte
+ * (2-byte types: 2-byte) alignment (MPI_ERR_ARG); a packed range or bounding
+ * range -- lowest run start to highest run end -- of 2^56 bytes or more
+ * (MPI_ERR_COUNT); a NULL `plan` (MPI_ERR_ARG).  On any error *plan is NULL.
+ * A table of zero elements is a valid plan.
+ *
+ * MPIX_Iov_plan_info reports (each pointer may be NULL) the packed elements,
+ * the runs after merging, the residue groups, the target's bounding byte
+ * range [lo_byte, hi_byte) relative to the target pointer (lo_byte may be
+ * negative; both 0 for an empty plan) and the bytes of table one device holds
+ * (0 for a plan of at most one run, which needs none).
+ *
+ * MPIX_Iov_plan_prepare copies the tables into the memory of `device` (-1: the
+ * current one).  It blocks and may allocate; it is idempotent and thread-safe.
+ * A launch on a device whose tables are missing prepares them itself first, so
+ * ONLY CALLS MADE AFTER prepare FOR THEIR DEVICE are free of allocation, copies
+ * and host synchronisation, and only those may be captured in a graph.  After
+ * it a call makes no allocation, no copy, no event call and no wait, and any
+ * number of threads and streams may use one plan at once: the plan is immutable
+ * apart from its per-device table set, which sits behind a mutex.
+ * One exception: a plan of exactly one run takes the contiguous entries' path
+ * (below), and with it their one piece of shared state.  In the reduce form the
+ * split combiners (the x87 and binary128 types' ops) use the per-(device,
+ * stream) fixup buffer of MPIX_Reduce_local_async: its first use on a stream,
+ * and a later call that needs a larger one, take a global mutex and may
+ * allocate or synchronise that stream.  So for such a plan, type and op, run one
+ * call of at least that size on the stream before capturing or relying on a
+ * call not to block -- exactly what MPIX_Reduce_local_async itself asks for.
+ * Every other single-run call, the fetch form included, holds to the rule.
+ *
+ * MPIX_Iov_plan_free releases the device tables (hipFree synchronises the
+ * device) and the host tables and sets *plan = NULL; freeing a NULL plan is a
+ * no-op.  Work still queued on the plan, and a captured graph that references
+ * it, are the caller's to finish or drop first.  MPIX_Redop_finalize does not
+ * free plans.
+ *
+ * MPIX_Reduce_local_plan* and MPIX_Get_accumulate_local_plan* do exactly what
+ * MPIX_Reduce_local_iov[ec]_async and MPIX_Get_accumulate_local_iov[ec]_async do
+ * given the table the plan was created from: the target, every gap and padding
+ * byte included, is bit-identical; the result receives the type map only;
+ * MPI_NO_OP fetches (origin may be NULL) and does nothing in the reduce form;
+ * MPI_REPLACE swaps in the fetch form and scatters in the reduce form.  One
+ * launch per residue group.  A plan of exactly one run takes the contiguous
+ * entries' path (MPIX_Reduce_local_async, MPIX_Get_accumulate_local_async) with
+ * the target at the run's offset.
+ *
+ * Checks, all before any device work, in this order: a NULL plan
+ * (MPI_ERR_ARG); a non-builtin op, an illegal (op, plan type) or MPIX_EQUAL
+ * (MPI_ERR_OP); a plan of zero elements then succeeds without looking at a
+ * pointer; NULL or MPI_IN_PLACE operands, the origin exempt under MPI_NO_OP in
+ * the fetch form (MPI_ERR_BUFFER); any overlap among the packed ranges and the
+ * plan's bounding range, the reduce form checking source against target the
+ * same way -- O(1) (MPI_ERR_BUFFER); a legal pair without a kernel (bf16 other
+ * than SUM: MPI_ERR_TYPE); an operand the stream's device cannot dereference
+ * (MPI_ERR_BUFFER).
+ *
+ * The async forms take what a kernel on `stream` can dereference.  The sync
+ * forms need a device-memory target, run on the calling thread's library
+ * stream and return when the results are visible, as
+ * MPIX_Get_accumulate_local. */
+typedef struct MPIX_Iov_plan_s *MPIX_Iov_plan;
+
+int MPIX_Iov_plan_create(MPIX_Aint nseg, const MPIX_Aint *seg_offsets, const MPIX_Aint *seg_counts,
+                         MPIX_Datatype basic_type, MPIX_Iov_plan *plan);
+int MPIX_Iov_plan_create_iovec(MPIX_Aint nseg, const MPIX_Aint *iov_offsets,
+                               const MPIX_Aint *iov_lens, MPIX_Datatype basic_type,
+                               MPIX_Iov_plan *plan);
+int MPIX_Iov_plan_prepare(MPIX_Iov_plan plan, int device);
+int MPIX_Iov_plan_info(MPIX_Iov_plan plan, MPIX_Aint *elements, MPIX_Aint *runs, MPIX_Aint *groups,
+                       MPIX_Aint *lo_byte, MPIX_Aint *hi_byte, MPIX_Aint *table_bytes);
+int MPIX_Iov_plan_free(MPIX_Iov_plan *plan);
+
+int MPIX_Reduce_local_plan_async(const void *inbuf, void *inoutbuf, MPIX_Iov_plan plan, MPIX_Op op,
+                                 void *stream);
+int MPIX_Reduce_local_plan(const void *inbuf, void *inoutbuf, MPIX_Iov_plan plan, MPIX_Op op);
+int MPIX_Get_accumulate_local_plan_async(const void *origin, void *result, void *target,
+                                         MPIX_Iov_plan plan, MPIX_Op op, void *stream);
+int MPIX_Get_accumulate_local_plan(const void *origin, void *result, void *target,
+                                   MPIX_Iov_plan plan, MPIX_Op op);
+
 /* ---- compare-and-swap ----
  * The local step of MPI_Compare_and_swap on one element (posix_rma.h:605-608,
  * mpidig_rma_callbacks.c:1059-1068):

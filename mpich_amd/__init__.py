@@ -17,4 +17,8 @@ def __getattr__(name):
     if name in ('redop', 'coll'):
         import importlib
         return importlib.import_module('.' + name, __name__)
+    # the committed iov plans of mpich_amd.redop, under the package's own name
+    if name in ('IovPlan', 'reduce_local_plan', 'get_accumulate_local_plan'):
+        import importlib
+        return getattr(importlib.import_module('.redop', __name__), name)
     raise AttributeError(name)

@@ -12,6 +12,7 @@
 #include <immintrin.h>
 
 #include <ctype.h>
+#include <limits.h>
 #include <pthread.h>
 #include <sched.h>
 #include <stdint.h>
@@ -2593,6 +2594,409 @@ int MPIX_Get_accumulate_local_iovec_async(const void *origin, void *result, void
         return set_err(rc);
     return set_err(getacc_runs(origin, result, target, runs, (uint32_t) basic_type, (uint32_t) op,
                                (hipStream_t) stream));
+}
+
+// ------------------------------------------------ committed iov plans
+// What MPI_Type_commit is to a datatype: the runs of one (table, basic type),
+// merged, grouped by residue and indexed per tile once, kept on the host and,
+// after MPIX_Iov_plan_prepare, resident on each device that uses them.  The
+// plan-taking entries then do no table work, no upload and no event call.
+// Immutable after create apart from `dev` (behind `mu`; a launch reads its
+// device's pointer with one acquire load).
+struct MPIX_Iov_plan_s {
+    uint32_t it = 0;
+    uint64_t ext = 0;
+    uint64_t total = 0;             // packed elements
+    int64_t nrun = 0;               // runs after the merge
+    int64_t lo = 0, hi = 0;         // the target's bounding byte range [lo, hi)
+    int64_t one_off = 0;            // nrun == 1: the run's byte offset
+    RunTable rt;                    // group_runs of the merged runs
+    std::vector<int32_t> tile;      // every group's tile index, group g from tile_base[g]
+    std::vector<size_t> tile_base;
+    size_t table_bytes = 0;         // device bytes: rt.tab, then tile (0: nothing to upload)
+    std::mutex mu;
+    std::atomic<char *> dev[kMaxDev];
+};
+
+// Merge, group and index the runs of a table whose type is already resolved.
+static int plan_build(std::vector<Run> &runs, uint32_t it, uint64_t ext, MPIX_Iov_plan *out)
+{
+    // total elements and the bounding byte range as the iov entries find them
+    // (getacc_runs): zero-length runs aside; sums through 128 bits, since
+    // n * ext may not fit 64 for a table about to be refused
+    const int64_t e = (int64_t) ext, align = e < 4 ? e : 4;
+    const uint64_t cap = ((uint64_t) 1 << 56) / ext;
+    const __int128 span_cap = (__int128) 1 << 56;
+    uint64_t total = 0;
+    __int128 lo = 0, hi = 0;
+    bool over = false, any = false;
+    for (const Run &r : runs) {
+        if (r.n == 0)
+            continue;
+        if ((uint64_t) r.n > cap || total + (uint64_t) r.n > cap) {
+            over = true;
+            break;
+        }
+        total += (uint64_t) r.n;
+        const __int128 a = r.off, b = a + (__int128) r.n * e;
+        if (!any || a < lo)
+            lo = a;
+        if (!any || b > hi)
+            hi = b;
+        any = true;
+    }
+    // a table of zero elements is a valid plan whatever its offsets are, as
+    // the entries succeed on it; otherwise every run's residue counts
+    if (over || total != 0) {
+        for (const Run &r : runs)
+            if ((((r.off % e) + e) % e) % align)
+                return MPIX_REDOP_ERR_ARG;
+        if (over || hi - lo >= span_cap || (__int128) total * e >= span_cap)
+            return MPIX_REDOP_ERR_COUNT;
+    }
+    // merge in call order: run k+1 starting where run k ends continues it (its
+    // packed elements follow run k's by construction); zero-length runs drop
+    // out, so one between two such runs does not keep them apart
+    size_t m = 0;
+    for (size_t k = 0; k < runs.size(); ++k) {
+        const Run r = runs[k];
+        if (r.n == 0)
+            continue;
+        if (m > 0 && (__int128) runs[m - 1].off + (__int128) runs[m - 1].n * e == (__int128) r.off)
+            runs[m - 1].n += r.n;
+        else
+            runs[m++] = r;
+    }
+    runs.resize(m);
+    if (!out)
+        return MPIX_REDOP_ERR_ARG;
+    MPIX_Iov_plan_s *p = new MPIX_Iov_plan_s;
+    for (auto &d : p->dev)
+        d.store(nullptr, std::memory_order_relaxed);
+    p->it = it;
+    p->ext = ext;
+    p->total = total;
+    p->nrun = (int64_t) m;
+    p->lo = (int64_t) lo;
+    p->hi = (int64_t) hi;
+    if (m == 1)
+        p->one_off = runs[0].off;
+    if (m > 1) {        // a single run takes the contiguous path: no table
+        group_runs(runs, e, &p->rt);
+        const size_t ng = p->rt.resid.size();
+        p->tile_base.resize(ng);
+        size_t need = 0;
+        for (size_t g = 0; g < ng; ++g) {
+            p->tile_base[g] = need;
+            need += (size_t) (((uint64_t) p->rt.gtotal[g] + 255) / 256) + 1;
+        }
+        p->tile.resize(need);
+        for (size_t g = 0; g < ng; ++g) {
+            const int64_t n = (int64_t) p->rt.nrun[g];
+            const int64_t *prefix = p->rt.tab.data() + p->rt.base[g] + n;
+            int32_t *tl = p->tile.data() + p->tile_base[g];
+            const uint64_t ntile = ((uint64_t) p->rt.gtotal[g] + 255) / 256;
+            int64_t s = 0;
+            for (uint64_t t = 0; t < ntile; ++t) {
+                while (s + 1 < n && (uint64_t) prefix[s + 1] <= t * 256)
+                    ++s;
+                tl[t] = (int32_t) s;
+            }
+            tl[ntile] = (int32_t) (n - 1);
+        }
+        p->table_bytes = p->rt.tab.size() * sizeof(int64_t) + p->tile.size() * sizeof(int32_t);
+    }
+    *out = p;
+    return MPIX_REDOP_SUCCESS;
+}
+
+int MPIX_Iov_plan_create(MPIX_Aint nseg, const MPIX_Aint *seg_offsets, const MPIX_Aint *seg_counts,
+                         MPIX_Datatype basic_type, MPIX_Iov_plan *plan)
+{
+    if (plan)
+        *plan = nullptr;
+    if (nseg > (MPIX_Aint) INT_MAX)
+        return set_err(MPIX_REDOP_ERR_COUNT);       // typerep_op.c:111 asserts the same
+    std::vector<Run> runs;
+    int rc = runs_from_iov(nseg, seg_offsets, seg_counts, &runs);
+    if (rc != MPIX_REDOP_SUCCESS)
+        return set_err(rc);
+    const uint32_t it = to_internal((uint32_t) basic_type);
+    const uint64_t ext = it == kNull ? 0 : extent_of(it);
+    if (ext == 0)
+        return set_err(MPIX_REDOP_ERR_TYPE);
+    return set_err(plan_build(runs, it, ext, plan));
+}
+
+int MPIX_Iov_plan_create_iovec(MPIX_Aint nseg, const MPIX_Aint *iov_offsets,
+                               const MPIX_Aint *iov_lens, MPIX_Datatype basic_type,
+                               MPIX_Iov_plan *plan)
+{
+    if (plan)
+        *plan = nullptr;
+    if (nseg > (MPIX_Aint) INT_MAX)
+        return set_err(MPIX_REDOP_ERR_COUNT);
+    std::vector<Run> runs;
+    int rc = runs_from_iovec(nseg, iov_offsets, iov_lens, (uint32_t) basic_type, &runs);
+    if (rc != MPIX_REDOP_SUCCESS)
+        return set_err(rc);
+    const uint32_t it = to_internal((uint32_t) basic_type);
+    return set_err(plan_build(runs, it, extent_of(it), plan));
+}
+
+// The plan's tables on `dev`, uploaded if they are not there yet (blocking).
+static int plan_tables(MPIX_Iov_plan_s *p, int dev, char **tab)
+{
+    *tab = nullptr;
+    if (dev < 0 || dev >= kMaxDev)
+        return MPIX_REDOP_ERR_OTHER;
+    if (p->table_bytes == 0)
+        return MPIX_REDOP_SUCCESS;
+    if ((*tab = p->dev[dev].load(std::memory_order_acquire)))
+        return MPIX_REDOP_SUCCESS;
+    std::lock_guard<std::mutex> l(p->mu);
+    if ((*tab = p->dev[dev].load(std::memory_order_acquire)))
+        return MPIX_REDOP_SUCCESS;
+    DeviceGuard guard(dev);
+    char *d = nullptr;
+    int rc = hip_err(hipMalloc((void **) &d, p->table_bytes));
+    if (rc != MPIX_REDOP_SUCCESS) {
+        (void) hipGetLastError();
+        return rc;
+    }
+    const size_t tb = p->rt.tab.size() * sizeof(int64_t);
+    rc = hip_err(hipMemcpy(d, p->rt.tab.data(), tb, hipMemcpyHostToDevice));
+    if (rc == MPIX_REDOP_SUCCESS)
+        rc = hip_err(hipMemcpy(d + tb, p->tile.data(), p->tile.size() * sizeof(int32_t),
+                               hipMemcpyHostToDevice));
+    if (rc != MPIX_REDOP_SUCCESS) {
+        (void) hipFree(d);
+        return rc;
+    }
+    p->dev[dev].store(d, std::memory_order_release);
+    *tab = d;
+    return MPIX_REDOP_SUCCESS;
+}
+
+int MPIX_Iov_plan_prepare(MPIX_Iov_plan plan, int device)
+{
+    if (!plan)
+        return set_err(MPIX_REDOP_ERR_ARG);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        (void) hipGetLastError();
+        return set_err(MPIX_REDOP_ERR_OTHER);
+    }
+    if (device == -1 && hipGetDevice(&device) != hipSuccess)
+        return set_err(MPIX_REDOP_ERR_OTHER);
+    if (device < 0 || device >= ndev)
+        return set_err(MPIX_REDOP_ERR_ARG);
+    char *tab;
+    return set_err(plan_tables(plan, device, &tab));
+}
+
+int MPIX_Iov_plan_info(MPIX_Iov_plan plan, MPIX_Aint *elements, MPIX_Aint *runs, MPIX_Aint *groups,
+                       MPIX_Aint *lo_byte, MPIX_Aint *hi_byte, MPIX_Aint *table_bytes)
+{
+    if (!plan)
+        return set_err(MPIX_REDOP_ERR_ARG);
+    if (elements)
+        *elements = (MPIX_Aint) plan->total;
+    if (runs)
+        *runs = (MPIX_Aint) plan->nrun;
+    if (groups)     // a single run is one group, though it has no table
+        *groups = plan->nrun == 1 ? 1 : (MPIX_Aint) plan->rt.resid.size();
+    if (lo_byte)
+        *lo_byte = (MPIX_Aint) plan->lo;
+    if (hi_byte)
+        *hi_byte = (MPIX_Aint) plan->hi;
+    if (table_bytes)
+        *table_bytes = (MPIX_Aint) plan->table_bytes;
+    return set_err(MPIX_REDOP_SUCCESS);
+}
+
+int MPIX_Iov_plan_free(MPIX_Iov_plan *plan)
+{
+    if (!plan)
+        return set_err(MPIX_REDOP_ERR_ARG);
+    MPIX_Iov_plan_s *p = *plan;
+    *plan = nullptr;
+    if (!p)
+        return set_err(MPIX_REDOP_SUCCESS);
+    int rc = MPIX_REDOP_SUCCESS;
+    for (int d = 0; d < kMaxDev; ++d) {
+        char *t = p->dev[d].load(std::memory_order_acquire);
+        if (!t)
+            continue;
+        DeviceGuard guard(d);
+        const int rc2 = hip_err(hipFree(t));
+        rc = rc ? rc : rc2;
+    }
+    delete p;
+    return set_err(rc);
+}
+
+static const mpix::PlanEntry *plan_entry(uint32_t opi, uint32_t it)
+{
+    const uint32_t raw = is_struct_pair(it) ? it : (it & 0xffffff00u);
+    const mpix::PlanEntry *e = mpix::lookup_plan_fp((int) raw, (int) opi);
+    if (!e)
+        e = mpix::lookup_plan_int((int) raw, (int) opi);
+    if (!e)
+        e = mpix::lookup_plan_pair((int) raw, (int) opi);
+    return e;
+}
+
+// Checks 1-6 of the plan-taking entries (mpix_redop.h), none of which needs a
+// device.  origin NULL-able: the fetch form under MPI_NO_OP.  *n = 0 when there
+// is nothing to do.
+static int plan_validate(const void *origin, const void *result, const void *target,
+                         MPIX_Iov_plan_s *p, uint32_t op, bool fetch, uint64_t *n)
+{
+    *n = 0;
+    if (!p)
+        return MPIX_REDOP_ERR_ARG;
+    if (!is_builtin_op(op) || (op & 0xf) == 15 || !internal_ok(op, p->it))
+        return MPIX_REDOP_ERR_OP;
+    if (p->total == 0)
+        return MPIX_REDOP_SUCCESS;
+    const uint32_t opi = op & 0xf;
+    const bool reads_origin = !(fetch && opi == 14);
+    if ((fetch && no_buffer(result)) || no_buffer(target) || (reads_origin && no_buffer(origin)))
+        return MPIX_REDOP_ERR_BUFFER;
+    const uint64_t packed = p->total * p->ext, span = (uint64_t) (p->hi - p->lo);
+    const char *tlo = (const char *) target + p->lo;
+    if ((fetch && ranges_overlap(result, packed, tlo, span)) ||
+        (reads_origin && (ranges_overlap(origin, packed, tlo, span) ||
+                          (fetch && ranges_overlap(origin, packed, result, packed)))))
+        return MPIX_REDOP_ERR_BUFFER;
+    // a plan of one run launches through gpu_entry / getacc_entry instead: every
+    // table is instantiated over the same (type, op) list, so one lookup answers
+    // for all (tests/test_plan_cpu.py compares the error classes pair by pair)
+    if (opi < 13 && !plan_entry(opi, p->it))
+        return MPIX_REDOP_ERR_TYPE;     // a legal pair without a kernel
+    *n = p->total;
+    return MPIX_REDOP_SUCCESS;
+}
+
+// Validated arguments: operand placement, the device's tables, the launches
+// on `s` -- one per residue group; a plan of one run goes down the contiguous
+// entries' path with the target at the run's offset.  result == NULL: the
+// reduce form.
+static int plan_enqueue(const void *origin, void *result, void *target, MPIX_Iov_plan_s *p,
+                        uint32_t op, bool fetch, hipStream_t s)
+{
+    const uint32_t opi = op & 0xf;
+    const bool reads_origin = !(fetch && opi == 14);
+    const void *po = origin, *pr = result, *pt;
+    int launch = -2;
+    bool zc = false;
+    if ((fetch && !reachable(result, s, &launch, &pr, &zc)) ||
+        !reachable(target, s, &launch, &pt, &zc) ||
+        (reads_origin && !reachable(origin, s, &launch, &po, &zc)))
+        return MPIX_REDOP_ERR_BUFFER;
+    if (!fetch && opi == 14)
+        return MPIX_REDOP_SUCCESS;      // the reduce form's MPI_NO_OP
+    if (p->nrun == 1) {
+        char *t1 = (char *) pt + p->one_off;
+        if (!fetch)
+            return enqueue(po, t1, p->total, p->it, p->ext, op, s, nullptr, nullptr, 0, nullptr, zc);
+        if (opi == 13 || opi == 14) {
+            int rc = copy_blocks((void *) pr, 1, t1, 1, p->total, 1, p->it, p->ext, s);
+            if (rc == MPIX_REDOP_SUCCESS && opi == 13)
+                rc = copy_blocks(t1, 1, po, 1, p->total, 1, p->it, p->ext, s);
+            return rc;
+        }
+        const mpix::GetaccEntry *e = getacc_entry(opi, p->it);
+        if (!e)
+            return MPIX_REDOP_ERR_TYPE;
+        return hip_err(e->contig(po, (void *) pr, t1, p->total, params(), launch_cfg(zc), s));
+    }
+    const mpix::PlanEntry *en = opi < 13 ? plan_entry(opi, p->it) : nullptr;
+    if (opi < 13 && !en)
+        return MPIX_REDOP_ERR_TYPE;
+    if (launch == -2)
+        launch = stream_device(s);
+    char *tab;
+    int rc = plan_tables(p, launch, &tab);
+    if (rc != MPIX_REDOP_SUCCESS)
+        return rc;
+    PairMap pm{0, 0};
+    (void) padded_pair(p->it, &pm);
+    const int32_t *tiles = (const int32_t *) (tab + p->rt.tab.size() * sizeof(int64_t));
+    const int mode = !fetch ? 2 : (opi == 13 ? 1 : 0);
+    for (size_t g = 0; g < p->rt.resid.size() && rc == MPIX_REDOP_SUCCESS; ++g) {
+        const int64_t n = (int64_t) p->rt.nrun[g];
+        const int64_t *t = (const int64_t *) tab + p->rt.base[g];
+        const int32_t *tl = tiles + p->tile_base[g];
+        void *tg = (char *) pt + p->rt.resid[g];
+        const uint64_t gt = (uint64_t) p->rt.gtotal[g];
+        if (!en)
+            rc = hip_err(mpix::launch_plan_copy(mode, (uint32_t) p->ext, pm.value_bytes, pm.loc_off,
+                                                po, (void *) pr, tg, t, tl, n, gt, launch_cfg(), s));
+        else if (fetch)
+            rc = hip_err(en->getacc(po, (void *) pr, tg, t, tl, n, gt, params(), launch_cfg(), s));
+        else
+            rc = hip_err(en->reduce(po, tg, t, tl, n, gt, params(), launch_cfg(), s));
+    }
+    return rc;
+}
+
+static int plan_async(const void *origin, void *result, void *target, MPIX_Iov_plan plan,
+                      uint32_t op, bool fetch, hipStream_t s)
+{
+    uint64_t n;
+    int rc = plan_validate(origin, result, target, plan, op, fetch, &n);
+    if (rc != MPIX_REDOP_SUCCESS || n == 0)
+        return rc;
+    return plan_enqueue(origin, result, target, plan, op, fetch, s);
+}
+
+// the synchronous forms, as getacc_sync: a device-memory target, the calling
+// thread's library stream of that device, and a wait on it
+static int plan_sync(const void *origin, void *result, void *target, MPIX_Iov_plan plan,
+                     uint32_t op, bool fetch)
+{
+    uint64_t n;
+    int rc = plan_validate(origin, result, target, plan, op, fetch, &n);
+    if (rc != MPIX_REDOP_SUCCESS || n == 0)
+        return rc;
+    int dev = 0;
+    const void *dp;
+    if (classify(target, &dev, &dp) != Where::Device)
+        return MPIX_REDOP_ERR_BUFFER;
+    DeviceGuard guard(dev);
+    DevState *d = dev_state(dev);
+    if (!d)
+        return MPIX_REDOP_ERR_OTHER;
+    rc = plan_enqueue(origin, result, target, plan, op, fetch, d->s[0]);
+    const int rc2 = wait_stream(d, d->s[0]);
+    return rc ? rc : rc2;
+}
+
+int MPIX_Reduce_local_plan_async(const void *inbuf, void *inoutbuf, MPIX_Iov_plan plan, MPIX_Op op,
+                                 void *stream)
+{
+    return set_err(plan_async(inbuf, nullptr, inoutbuf, plan, (uint32_t) op, false,
+                              (hipStream_t) stream));
+}
+
+int MPIX_Reduce_local_plan(const void *inbuf, void *inoutbuf, MPIX_Iov_plan plan, MPIX_Op op)
+{
+    return set_err(plan_sync(inbuf, nullptr, inoutbuf, plan, (uint32_t) op, false));
+}
+
+int MPIX_Get_accumulate_local_plan_async(const void *origin, void *result, void *target,
+                                         MPIX_Iov_plan plan, MPIX_Op op, void *stream)
+{
+    return set_err(plan_async(origin, result, target, plan, (uint32_t) op, true,
+                              (hipStream_t) stream));
+}
+
+int MPIX_Get_accumulate_local_plan(const void *origin, void *result, void *target,
+                                   MPIX_Iov_plan plan, MPIX_Op op)
+{
+    return set_err(plan_sync(origin, result, target, plan, (uint32_t) op, true));
 }
 
 // MPI_Compare_and_swap's local step.  MPIR_Type_is_rma_atomic

@@ -136,6 +136,34 @@ hipError_t launch_getacc_iov_copy(bool replace, uint32_t extent, uint32_t value_
                                   const int64_t *d_src_off, int64_t nseg, uint64_t total,
                                   const LaunchCfg &, hipStream_t);
 
+// The reduce and the fetch form over a committed plan (MPIX_Iov_plan,
+// MPIX_*_local_plan*): one residue group's resident table d_tab =
+// [seg_off nseg][prefix nseg+1][src_off nseg] and its per-tile index d_tile
+// (the run holding packed index 256 t, closed by nseg - 1).  A table and units
+// of its own once more (inst_plan_*.hip); a pair has a PlanEntry exactly when
+// it has a GetaccIovEntry.
+struct PlanEntry {
+    hipError_t (*reduce)(const void *in, void *io, const int64_t *d_tab, const int32_t *d_tile,
+                         int64_t nseg, uint64_t total, const Params &, const LaunchCfg &,
+                         hipStream_t);
+    hipError_t (*getacc)(const void *origin, void *result, void *target, const int64_t *d_tab,
+                         const int32_t *d_tile, int64_t nseg, uint64_t total, const Params &,
+                         const LaunchCfg &, hipStream_t);
+};
+
+const PlanEntry *lookup_plan_int(int raw, int opi);
+const PlanEntry *lookup_plan_fp(int raw, int opi);
+const PlanEntry *lookup_plan_pair(int raw, int opi);
+
+// The type-map copies over the same tables: mode 0 gathers the runs into the
+// packed result (the fetch form's MPI_NO_OP), 1 also scatters the packed origin
+// over them (its MPI_REPLACE), 2 scatters only (the reduce form's MPI_REPLACE,
+// result unused).  Layouts as launch_getacc_iov_copy.  inst_plan_copy.hip.
+hipError_t launch_plan_copy(int mode, uint32_t extent, uint32_t value_bytes, uint32_t loc_off,
+                            const void *origin, void *result, void *target, const int64_t *d_tab,
+                            const int32_t *d_tile, int64_t nseg, uint64_t total,
+                            const LaunchCfg &, hipStream_t);
+
 // MPI_Compare_and_swap on one integer element of `size` bytes (1, 2, 4, 8,
 // 16): *result = *target; if (*target == *compare) *target = *origin.
 hipError_t launch_cas(uint32_t size, const void *origin, const void *compare, void *result,

@@ -1758,6 +1758,179 @@ template <class C> constexpr GetaccIovEntry getacc_iov_entry()
 }
 
 // ---------------------------------------------------------------------------
+// Committed iov plans (MPIX_Iov_plan_*, MPIX_*_local_plan*): the run table of
+// k_iov / k_getacc_iov, resident on the device, with one more table per
+// residue group: tile[t] = the run that holds packed index 256 t, closed by
+// tile[ntile] = nseg - 1.  One loop iteration of a 256-thread block covers
+// exactly tile t = block + i * nblk, so both bounds are loads from a
+// block-uniform address (scalar loads), and a lane's run lies in
+// [tile[t], tile[t + 1]]: no search when the two are equal, else a search of
+// `prefix` between them only.
+
+// How a lane finds its run: 0 = the per-tile index; 1 = iov_run<1>'s
+// wave-uniform search over the whole prefix table.  The choice is measured
+// (tools/getacc_rows.py plan, DESIGN.md "Committed iov plans").
+#ifndef MPIX_PLAN_LOOKUP
+#define MPIX_PLAN_LOOKUP 0
+#endif
+
+// The run of packed index j = 256 t + thread < total.
+template <int LOOKUP>
+__device__ __forceinline__ int64_t plan_run(const int64_t *__restrict__ prefix,
+                                            const int32_t *__restrict__ tile, int64_t nseg,
+                                            uint64_t t, uint64_t j, uint64_t total)
+{
+    if constexpr (LOOKUP == 0) {
+        const int64_t lo = tile[t], hi = tile[t + 1];       // block-uniform
+        if (lo == hi)
+            return lo;
+        return iov_search(prefix, lo, hi, j);
+    } else {
+        return iov_run<1>(prefix, nseg, j, total);
+    }
+}
+
+// k_iov's body: inout element = inout element OP packed source element.
+template <class C>
+__global__ void __launch_bounds__(256)
+k_plan_reduce(const typename C::unit *__restrict__ in, typename C::unit *__restrict__ io,
+              const int64_t *__restrict__ seg_off, const int64_t *__restrict__ prefix,
+              const int64_t *__restrict__ src_off, const int32_t *__restrict__ tile, int64_t nseg,
+              uint64_t total, Params prm, uint32_t nblk)
+{
+    for (uint64_t t = blockIdx.x; t * 256 < total; t += nblk) {     // 256-thread blocks
+        const uint64_t j = t * 256 + threadIdx.x;
+        if (j >= total)
+            break;
+        const int64_t s = plan_run<MPIX_PLAN_LOOKUP>(prefix, tile, nseg, t, j, total);
+        const int64_t k = (int64_t) (j - (uint64_t) prefix[s]);
+        const int64_t e = seg_off[s] + k;
+        io[e] = C::apply(io[e], in[src_off[s] + k], prm);
+    }
+}
+
+// k_getacc_iov's body: the old target element goes to the result through
+// FetchStore (type map only) and is combined; the full C::apply, no fixup
+// words, no shared state.
+template <class C>
+__global__ void __launch_bounds__(256)
+k_plan_getacc(const typename C::unit *__restrict__ in, typename C::unit *__restrict__ res,
+              typename C::unit *__restrict__ io, const int64_t *__restrict__ seg_off,
+              const int64_t *__restrict__ prefix, const int64_t *__restrict__ src_off,
+              const int32_t *__restrict__ tile, int64_t nseg, uint64_t total, Params prm,
+              uint32_t nblk)
+{
+    using T = typename C::unit;
+    for (uint64_t t = blockIdx.x; t * 256 < total; t += nblk) {
+        const uint64_t j = t * 256 + threadIdx.x;
+        if (j >= total)
+            break;
+        const int64_t s = plan_run<MPIX_PLAN_LOOKUP>(prefix, tile, nseg, t, j, total);
+        const int64_t k = (int64_t) (j - (uint64_t) prefix[s]);
+        const int64_t e = seg_off[s] + k, p = src_off[s] + k;
+        const T a = io[e];
+        FetchStore<T>::st(res + p, a);
+        io[e] = C::apply(a, in[p], prm);
+    }
+}
+
+// The type-map copies over a plan, k_getacc_iov_copy's unit bodies: gather
+// (the fetch form's MPI_NO_OP), swap (its MPI_REPLACE) and scatter (the reduce
+// form's MPI_REPLACE: the packed source's type map over the runs, no result).
+enum PlanCopy { kPlanGather = 0, kPlanSwap = 1, kPlanScatter = 2 };
+
+template <class T, int MODE>
+__global__ void __launch_bounds__(256)
+k_plan_copy(const T *__restrict__ in, T *__restrict__ res, T *__restrict__ io,
+            const int64_t *__restrict__ seg_off, const int64_t *__restrict__ prefix,
+            const int64_t *__restrict__ src_off, const int32_t *__restrict__ tile, int64_t nseg,
+            uint64_t total, uint32_t nblk)
+{
+    for (uint64_t t = blockIdx.x; t * 256 < total; t += nblk) {
+        const uint64_t j = t * 256 + threadIdx.x;
+        if (j >= total)
+            break;
+        const int64_t s = plan_run<MPIX_PLAN_LOOKUP>(prefix, tile, nseg, t, j, total);
+        const int64_t k = (int64_t) (j - (uint64_t) prefix[s]);
+        const int64_t e = seg_off[s] + k, p = src_off[s] + k;
+        if constexpr (MODE != kPlanScatter) {
+            const T a = io[e];
+            FetchStore<T>::st(res + p, a);
+        }
+        if constexpr (MODE != kPlanGather) {
+            const T b = in[p];
+            FetchStore<T>::st(io + e, b);
+        }
+    }
+}
+
+// One residue group's device table as the host lays it out (MPIX_Iov_plan_s in
+// redop_capi.cpp: its RunTable, group g from base[g]): [seg_off n][prefix n+1]
+// [src_off n]; the group's tile index is passed beside it (tile_base[g]).
+template <class C>
+hipError_t launch_plan_reduce(const void *in, void *io, const int64_t *d_tab,
+                              const int32_t *d_tile, int64_t nseg, uint64_t total,
+                              const Params &prm, const LaunchCfg &cfg, hipStream_t s)
+{
+    using T = typename C::unit;
+    if (total == 0 || nseg == 0)
+        return hipSuccess;
+    Params p = prm;
+    p.done = nullptr;
+    p.fixup = nullptr;
+    const unsigned grid = grid_for(256ull * 4, total, cfg.max_grid, 256);
+    hipLaunchKernelGGL((k_plan_reduce<C>), dim3(grid), dim3(256), 0, s, static_cast<const T *>(in),
+                       static_cast<T *>(io), d_tab, d_tab + nseg, d_tab + 2 * nseg + 1, d_tile,
+                       nseg, total, p, grid);
+    return hipGetLastError();
+}
+
+template <class C>
+hipError_t launch_plan_getacc(const void *in, void *res, void *io, const int64_t *d_tab,
+                              const int32_t *d_tile, int64_t nseg, uint64_t total,
+                              const Params &prm, const LaunchCfg &cfg, hipStream_t s)
+{
+    using T = typename C::unit;
+    if (total == 0 || nseg == 0)
+        return hipSuccess;
+    Params p = prm;
+    p.done = nullptr;
+    p.fixup = nullptr;
+    const unsigned grid = grid_for(256ull * 4, total, cfg.max_grid, 256);
+    hipLaunchKernelGGL((k_plan_getacc<C>), dim3(grid), dim3(256), 0, s, static_cast<const T *>(in),
+                       static_cast<T *>(res), static_cast<T *>(io), d_tab, d_tab + nseg,
+                       d_tab + 2 * nseg + 1, d_tile, nseg, total, p, grid);
+    return hipGetLastError();
+}
+
+template <class T>
+hipError_t launch_plan_copy_as(int mode, const void *in, void *res, void *io, const int64_t *d_tab,
+                               const int32_t *d_tile, int64_t nseg, uint64_t total,
+                               const LaunchCfg &cfg, hipStream_t s)
+{
+    if (total == 0 || nseg == 0)
+        return hipSuccess;
+    const unsigned grid = grid_for(256ull * 4, total, cfg.max_grid, 256);
+#define MPIX_PLAN_COPY(MODE)                                                                    \
+    hipLaunchKernelGGL((k_plan_copy<T, MODE>), dim3(grid), dim3(256), 0, s,                     \
+                       static_cast<const T *>(in), static_cast<T *>(res), static_cast<T *>(io), \
+                       d_tab, d_tab + nseg, d_tab + 2 * nseg + 1, d_tile, nseg, total, grid)
+    switch (mode) {
+        case kPlanGather: MPIX_PLAN_COPY(kPlanGather); break;
+        case kPlanSwap: MPIX_PLAN_COPY(kPlanSwap); break;
+        case kPlanScatter: MPIX_PLAN_COPY(kPlanScatter); break;
+        default: return hipErrorInvalidValue;
+    }
+#undef MPIX_PLAN_COPY
+    return hipGetLastError();
+}
+
+template <class C> constexpr PlanEntry plan_entry()
+{
+    return PlanEntry{&launch_plan_reduce<C>, &launch_plan_getacc<C>};
+}
+
+// ---------------------------------------------------------------------------
 // MPI_Compare_and_swap's local step on one element of 1, 2, 4, 8 or 16 bytes
 // (posix_rma.h:605-608): plain loads and stores, stream-ordered like every
 // other entry; the four addresses need no alignment.

@@ -6,6 +6,7 @@
 #   make -f sanitize.mk SAN=asan   # AddressSanitizer + UndefinedBehaviorSanitizer
 #   make -f sanitize.mk SAN=tsan   # ThreadSanitizer (the in-process transport's mailbox)
 # Outputs in build/$(SAN)/ (git-ignored); run build/$(SAN)/coll_host_sanitize.
+# tests/c/plan_host_check.cpp is built on request (see its rule below).
 SAN ?= asan
 CXX ?= g++
 CC ?= gcc
@@ -21,7 +22,8 @@ HOSTFLAGS = -O1 -g -fno-omit-frame-pointer -std=c++17 -fPIC -Wall -D__HIP_PLATFO
 KOBJS = build/inst_int.o build/inst_fp.o build/inst_pair.o \
         build/inst_getacc_int.o build/inst_getacc_fp.o build/inst_getacc_pair.o \
         build/inst_getacc_iov_int.o build/inst_getacc_iov_fp.o build/inst_getacc_iov_pair.o \
-        build/inst_getacc_copy.o
+        build/inst_getacc_copy.o \
+        build/inst_plan_int.o build/inst_plan_fp.o build/inst_plan_pair.o build/inst_plan_copy.o
 
 all: $(OUT)/coll_host_sanitize
 
@@ -50,6 +52,14 @@ $(OUT)/coll_host_sanitize: ../../tests/c/coll_host_sanitize.c $(OUT)/libmpix_col
 	    -I../../include -I/opt/rocm/include -o $@ $< -L$(OUT) -lmpix_coll -lmpix_redop \
 	    -L$(ORACLE) -loracle_redop -lpthread \
 	    -Wl,-rpath,$(abspath $(OUT)) -Wl,-rpath,$(abspath $(ORACLE)) -Wl,-rpath,/opt/rocm/lib
+
+# the committed iov plans' host side (create / info / free and the launch
+# entries' device-free checks), a goal of its own:
+#   make -f sanitize.mk SAN=asan build/asan/plan_host_check
+$(OUT)/plan_host_check: ../../tests/c/plan_host_check.cpp $(OUT)/libmpix_redop.so
+	$(CXX) -std=c++17 -O1 -g -fno-omit-frame-pointer -Wall $(SANFLAGS) -D__HIP_PLATFORM_AMD__ \
+	    -I../../include -I/opt/rocm/include -o $@ $< -L$(OUT) -lmpix_redop \
+	    -Wl,-rpath,$(abspath $(OUT)) -Wl,-rpath,/opt/rocm/lib
 
 clean:
 	rm -rf $(OUT)

@@ -65,6 +65,17 @@ def lib():
                                                      ctypes.POINTER(aint), i32, i32, vp], i32),
             'MPIX_Get_accumulate_local_iovec_async': ([vp, vp, vp, aint, ctypes.POINTER(aint),
                                                        ctypes.POINTER(aint), i32, i32, vp], i32),
+            'MPIX_Iov_plan_create': ([aint, ctypes.POINTER(aint), ctypes.POINTER(aint), i32,
+                                      ctypes.POINTER(vp)], i32),
+            'MPIX_Iov_plan_create_iovec': ([aint, ctypes.POINTER(aint), ctypes.POINTER(aint), i32,
+                                            ctypes.POINTER(vp)], i32),
+            'MPIX_Iov_plan_prepare': ([vp, i32], i32),
+            'MPIX_Iov_plan_info': ([vp] + [ctypes.POINTER(aint)] * 6, i32),
+            'MPIX_Iov_plan_free': ([ctypes.POINTER(vp)], i32),
+            'MPIX_Reduce_local_plan_async': ([vp, vp, vp, i32, vp], i32),
+            'MPIX_Reduce_local_plan': ([vp, vp, vp, i32], i32),
+            'MPIX_Get_accumulate_local_plan_async': ([vp, vp, vp, vp, i32, vp], i32),
+            'MPIX_Get_accumulate_local_plan': ([vp, vp, vp, vp, i32], i32),
             'MPIX_Compare_and_swap_local': ([vp, vp, vp, vp, i32], i32),
             'MPIX_Compare_and_swap_local_async': ([vp, vp, vp, vp, i32, vp], i32),
             'MPIX_Redop_is_supported': ([i32, aint, i32], i32),
@@ -359,6 +370,110 @@ def get_accumulate_local_iovec(origin, result, target, iov_offsets, iov_lens, ba
     return lib().MPIX_Get_accumulate_local_iovec_async(
         _addr(origin), _addr(result), _addr(target), n, offs, lens, H.as_c_int(basic_type),
         H.as_c_int(op), _stream_ptr(stream))
+
+
+class IovPlan:
+    """A committed iov plan (MPIX_Iov_plan): the run table of one derived
+    target built once -- merged, grouped and indexed on the host at creation,
+    resident on a device after prepare() -- and reused by reduce_local_plan /
+    get_accumulate_local_plan.  Creation makes no HIP call.  Close it (or use
+    it as a context manager) once no queued work references it."""
+
+    def __init__(self, create, offsets, second, basic_type):
+        n = len(offsets)
+        if len(second) != n:
+            raise ValueError('the two tables must have one entry per segment')
+        offs = (ctypes.c_ssize_t * max(n, 1))(*offsets)     # built once, read by create only
+        sec = (ctypes.c_ssize_t * max(n, 1))(*second)
+        self._h = ctypes.c_void_p()
+        self.basic_type = basic_type
+        check(create(n, offs, sec, H.as_c_int(basic_type), ctypes.byref(self._h)),
+              'MPIX_Iov_plan_create')
+        self._info = None
+        self._ext = datatype_extent(basic_type)
+
+    @classmethod
+    def from_iov(cls, seg_offsets, seg_counts, basic_type):
+        """byte offsets and element counts, as reduce_local_iov_async takes them"""
+        return cls(lib().MPIX_Iov_plan_create, seg_offsets, seg_counts, basic_type)
+
+    @classmethod
+    def from_iovec(cls, iov_offsets, iov_lens, basic_type):
+        """byte offsets and byte lengths, as reduce_local_iovec_async takes them"""
+        return cls(lib().MPIX_Iov_plan_create_iovec, iov_offsets, iov_lens, basic_type)
+
+    @property
+    def handle(self):
+        if not self._h:
+            raise ValueError('the plan is closed')
+        return self._h
+
+    def prepare(self, device=-1):
+        """copy the tables to `device` (-1: the current one); blocking,
+        idempotent.  Returns an MPI error class."""
+        return lib().MPIX_Iov_plan_prepare(self.handle, int(device))
+
+    def info(self):
+        """dict(elements, runs, groups, lo_byte, hi_byte, table_bytes)"""
+        if self._info is None:
+            v = [ctypes.c_ssize_t() for _ in range(6)]
+            check(lib().MPIX_Iov_plan_info(self.handle, *[ctypes.byref(x) for x in v]),
+                  'MPIX_Iov_plan_info')
+            self._info = dict(zip(('elements', 'runs', 'groups', 'lo_byte', 'hi_byte',
+                                   'table_bytes'), (x.value for x in v)))
+        return dict(self._info)
+
+    def close(self):
+        if self._h:
+            check(lib().MPIX_Iov_plan_free(ctypes.byref(self._h)), 'MPIX_Iov_plan_free')
+            self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:       # interpreter shutdown
+            pass
+
+
+def _plan_ranges(plan, origin, result, target):
+    """the mirror's range checks of a plan call, from the plan's own info"""
+    i = plan.info() if plan._ext > 0 else None
+    if not i or i['elements'] == 0:
+        return
+    packed = i['elements'] * plan._ext
+    _range_check(target, i['lo_byte'], i['hi_byte'], 'plan target')
+    if result is not None:
+        _range_check(result, 0, packed, 'packed result')
+    if origin is not None:
+        _range_check(origin, 0, packed, 'packed origin')
+
+
+def reduce_local_plan(inbuf, inoutbuf, plan, op, sync=False, stream=None):
+    """reduce_local_iov[ec]_async over a committed plan: no table work, no
+    upload and no event call once the plan is prepared on the stream's device"""
+    _plan_ranges(plan, inbuf, None, inoutbuf)
+    if sync:
+        return lib().MPIX_Reduce_local_plan(_addr(inbuf), _addr(inoutbuf), plan.handle,
+                                            H.as_c_int(op))
+    return lib().MPIX_Reduce_local_plan_async(_addr(inbuf), _addr(inoutbuf), plan.handle,
+                                              H.as_c_int(op), _stream_ptr(stream))
+
+
+def get_accumulate_local_plan(origin, result, target, plan, op, sync=False, stream=None):
+    """get_accumulate_local_iov[ec] over a committed plan; `origin` may be
+    None for MPI_NO_OP.  sync=True: the blocking form (device-memory target)."""
+    _plan_ranges(plan, origin, result, target)
+    args = (_addr(origin), _addr(result), _addr(target), plan.handle, H.as_c_int(op))
+    if sync:
+        return lib().MPIX_Get_accumulate_local_plan(*args)
+    return lib().MPIX_Get_accumulate_local_plan_async(*args, _stream_ptr(stream))
 
 
 def compare_and_swap_local(origin, compare, result, target, datatype, stream=None, sync=False):

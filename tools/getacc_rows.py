@@ -33,7 +33,17 @@ N s bytes, and, row A only, (memcpy_per_run) one hipMemcpyAsync per run
 followed by the reduce call: what a caller had before these entries.  The
 events bracket whole calls, so the host's table building shows wherever it
 outlasts the kernels.  Compare builds by running once per build, e.g. the run
-lookup: EXTRA_FLAGS=-DMPIX_GETACC_IOV_LOOKUP=n."""
+lookup: EXTRA_FLAGS=-DMPIX_GETACC_IOV_LOOKUP=n.
+
+       getacc_rows.py LIBPATH LABEL plan [ROWS]
+The same rows through a committed plan (MPIX_Iov_plan_*), same method: per row
+(plan_fetch) MPIX_Get_accumulate_local_plan_async and (plan_reduce)
+MPIX_Reduce_local_plan_async after MPIX_Iov_plan_prepare, each against its
+yardstick on the same table, (iov_fetch) MPIX_Get_accumulate_local_iov[ec]_async
+and (iov_reduce) MPIX_Reduce_local_iov[ec]_async; plus the host's wall time of
+MPIX_Iov_plan_create[_iovec] and of MPIX_Iov_plan_prepare (median of 3), and
+what MPIX_Iov_plan_info reports.  Compare the run lookups by running once per
+build: EXTRA_FLAGS=-DMPIX_PLAN_LOOKUP=n."""
 import ctypes
 import json
 import os
@@ -238,6 +248,114 @@ def iov_main():
                           rows=rows)))
 
 
+def plan_row(name, tn, on, nseg, packed_bytes, t, info, create_ms, prepare_ms):
+    med = {k: v[len(v) // 2] for k, v in t.items()}
+    r = dict(row=name, type=tn, op=on, segments=nseg, packed_bytes=packed_bytes, **info,
+             create_ms=round(create_ms, 3), prepare_ms=round(prepare_ms, 3))
+    for k, v in t.items():
+        r[k + '_ms'] = round(med[k], 4)
+        r[k + '_spread_ms'] = [round(v[0], 4), round(v[-1], 4)]
+    for form in ('fetch', 'reduce'):
+        a, b = t['plan_' + form], t['iov_' + form]
+        r[form + '_ratio_to_iov'] = round(med['plan_' + form] / med['iov_' + form], 4)
+        spread = max(a[-1] - a[0], b[-1] - b[0])
+        # not slower than its yardstick by more than the batches' spread
+        r[form + '_holds'] = bool(med['plan_' + form] <= med['iov_' + form] + spread)
+    r['plan_fetch_TBs'] = round(4 * packed_bytes / (med['plan_fetch'] * 1e-3) / 1e12, 3)
+    r['plan_reduce_TBs'] = round(3 * packed_bytes / (med['plan_reduce'] * 1e-3) / 1e12, 3)
+    return r
+
+
+def plan_main():
+    import time
+    import numpy as np
+    which = sys.argv[4] if len(sys.argv) > 4 else 'ABCD'
+    iov_sig = [vp, vp, vp, aint, vp, vp, i32, i32, vp]
+    L.MPIX_Get_accumulate_local_iov_async.argtypes = iov_sig
+    L.MPIX_Get_accumulate_local_iovec_async.argtypes = iov_sig
+    L.MPIX_Reduce_local_iov_async.argtypes = iov_sig[1:]
+    L.MPIX_Reduce_local_iovec_async.argtypes = iov_sig[1:]
+    L.MPIX_Iov_plan_create.argtypes = [aint, vp, vp, i32, ctypes.POINTER(vp)]
+    L.MPIX_Iov_plan_create_iovec.argtypes = [aint, vp, vp, i32, ctypes.POINTER(vp)]
+    L.MPIX_Iov_plan_prepare.argtypes = [vp, i32]
+    L.MPIX_Iov_plan_info.argtypes = [vp] + [ctypes.POINTER(aint)] * 6
+    L.MPIX_Iov_plan_free.argtypes = [ctypes.POINTER(vp)]
+    L.MPIX_Reduce_local_plan_async.argtypes = [vp, vp, vp, i32, vp]
+    L.MPIX_Get_accumulate_local_plan_async.argtypes = [vp, vp, vp, vp, i32, vp]
+    dev = torch.device('cuda', 0)
+    t8 = torch.empty(1 << 30, dtype=torch.uint8, device=dev)
+    o8, r8 = (torch.empty(1 << 29, dtype=torch.uint8, device=dev) for _ in range(2))
+    s = torch.cuda.current_stream()
+    sp = s.cuda_stream
+    tp, op_, rp = t8.data_ptr(), o8.data_ptr(), r8.data_ptr()
+    shapes = dict(A=(1024, 65536), B=(131072, 512), C=(1 << 20, 8))
+    rows = []
+    for name in 'ABCD':
+        if name not in which:
+            continue
+        if name == 'D':
+            n = 32 << 20
+            tn, on, kind, nseg, packed = 'MPI_DOUBLE_INT', 'MPI_MAXLOC', 'double_int', 2 * n, n * 16
+            offs = np.empty(nseg, np.int64)
+            offs[0::2] = np.arange(n, dtype=np.int64) * 16
+            offs[1::2] = offs[0::2] + 8
+            second = np.empty(nseg, np.int64)
+            second[0::2], second[1::2] = 8, 4
+            create, fetch, reduce = (L.MPIX_Iov_plan_create_iovec,
+                                     L.MPIX_Get_accumulate_local_iovec_async,
+                                     L.MPIX_Reduce_local_iovec_async)
+            fill(t8[:packed], kind, 0x5EED0B13)
+        else:
+            nseg, n = shapes[name]
+            tn, on, kind, packed = 'MPI_DOUBLE', 'MPI_SUM', 'fp64', nseg * n * 8
+            offs = np.arange(nseg, dtype=np.int64) * (2 * n * 8)
+            second = np.full(nseg, n, np.int64)
+            create, fetch, reduce = (L.MPIX_Iov_plan_create, L.MPIX_Get_accumulate_local_iov_async,
+                                     L.MPIX_Reduce_local_iov_async)
+            fill(t8, kind, 0x5EED0B11)
+        fill(o8, kind, 0x5EED0B12)
+        dt, op = H.as_c_int(getattr(H, tn)), H.as_c_int(getattr(H, on))
+        po, ps = offs.ctypes.data, second.ctypes.data
+        torch.cuda.synchronize()
+        plan, tc, tprep = vp(), [], []
+        for _ in range(3):      # a fresh plan each time: prepare is idempotent on one
+            if plan:
+                ok(L.MPIX_Iov_plan_free(ctypes.byref(plan)), 'MPIX_Iov_plan_free')
+            t0 = time.perf_counter()
+            ok(create(nseg, po, ps, dt, ctypes.byref(plan)), 'MPIX_Iov_plan_create')
+            t1 = time.perf_counter()
+            ok(L.MPIX_Iov_plan_prepare(plan, 0), 'MPIX_Iov_plan_prepare')
+            t2 = time.perf_counter()
+            tc.append((t1 - t0) * 1e3)
+            tprep.append((t2 - t1) * 1e3)
+        v = [aint() for _ in range(6)]
+        ok(L.MPIX_Iov_plan_info(plan, *[ctypes.byref(x) for x in v]), 'MPIX_Iov_plan_info')
+        info = dict(elements=v[0].value, runs=v[1].value, groups=v[2].value,
+                    table_bytes=v[5].value)
+
+        def plan_fetch():
+            ok(L.MPIX_Get_accumulate_local_plan_async(op_, rp, tp, plan, op, sp),
+               'MPIX_Get_accumulate_local_plan_async')
+
+        def iov_fetch():
+            ok(fetch(op_, rp, tp, nseg, po, ps, dt, op, sp), 'the fetch entry')
+
+        def plan_reduce():
+            ok(L.MPIX_Reduce_local_plan_async(op_, tp, plan, op, sp), 'MPIX_Reduce_local_plan_async')
+
+        def iov_reduce():
+            ok(reduce(op_, tp, nseg, po, ps, dt, op, sp), 'the reduce entry')
+        t = timed_forms(dict(plan_fetch=plan_fetch, iov_fetch=iov_fetch, plan_reduce=plan_reduce,
+                             iov_reduce=iov_reduce), s)
+        rows.append(plan_row(name, tn, on, nseg, packed, t, info, sorted(tc)[1], sorted(tprep)[1]))
+        torch.cuda.synchronize()
+        ok(L.MPIX_Iov_plan_free(ctypes.byref(plan)), 'MPIX_Iov_plan_free')
+    L.MPIX_Redop_build_info.restype = ctypes.c_char_p
+    print(json.dumps(dict(label=sys.argv[2], lib=os.path.basename(sys.argv[1]),
+                          build=L.MPIX_Redop_build_info().decode(), batches=BATCHES, reps=REPS,
+                          rows=rows)))
+
+
 def main():
     nbytes = 1 << 30
     dev = torch.device('cuda', 0)
@@ -294,5 +412,7 @@ def main():
 if __name__ == '__main__':
     if len(sys.argv) > 3 and sys.argv[3] == 'iov':
         iov_main()
+    elif len(sys.argv) > 3 and sys.argv[3] == 'plan':
+        plan_main()
     else:
         main()

@@ -1,56 +1,12 @@
-// inst_getacc_fp.hip -- the fused get-accumulate kernels of the floating-point
-// and complex combiners: inst_fp.hip's (type, op) table over getacc_entry.
-#include "redop_kernels.h"
+// inst_getacc_fp.hip -- the fused get-accumulate kernels
+// of the floating-point and complex combiners: redop_tables.h's fp table over MakeGetacc.
+#include "redop_tables.h"
 
 namespace mpix {
 
-namespace {
-
-template <class Max, class Min, class Sum, class Prod>
-const GetaccEntry *four_ops(int opi)
-{
-    static const GetaccEntry tab[4] = { getacc_entry<Max>(), getacc_entry<Min>(),
-                                        getacc_entry<Sum>(), getacc_entry<Prod>() };
-    return (opi >= 1 && opi <= 4) ? &tab[opi - 1] : nullptr;
-}
-
-template <typename T>
-const GetaccEntry *real_ops(int opi)
-{
-    return four_ops<FMax<T>, FMin<T>, FSum<T>, FProd<T>>(opi);
-}
-
-template <class Sum, class Prod>
-const GetaccEntry *cplx_ops(int opi)
-{
-    static const GetaccEntry tab[2] = { getacc_entry<Sum>(), getacc_entry<Prod>() };
-    return (opi == 3 || opi == 4) ? &tab[opi - 3] : nullptr;
-}
-
-const GetaccEntry *bf16_ops(int opi)
-{
-    static const GetaccEntry e = getacc_entry<Bf16Sum>();
-    return opi == 3 ? &e : nullptr;     // only MPIR_SUM handles MPIR_BFLOAT16
-}
-
-}  // namespace
-
 const GetaccEntry *lookup_getacc_fp(int raw, int opi)
 {
-    switch ((unsigned) raw) {
-        case 0x4c830200u: return real_ops<_Float16>(opi);
-        case 0x4c830400u: return real_ops<float>(opi);
-        case 0x4c830800u: return real_ops<double>(opi);
-        case 0x4c840400u: return cplx_ops<CSum<_Float16>, CProdHalf>(opi);
-        case 0x4c840800u: return cplx_ops<CSum<float>, CProdAnnexG<float>>(opi);
-        case 0x4c841000u: return cplx_ops<CSum<double>, CProdAnnexG<double>>(opi);
-        case 0x4c850200u: return bf16_ops(opi);
-        case 0x4c851000u: return four_ops<X87Max, X87Min, X87Sum, X87Prod>(opi);
-        case 0x4c831000u: return four_ops<QuadMax, QuadMin, QuadSum, QuadProd>(opi);
-        case 0x4c842000u: return cplx_ops<QuadCSum, QuadCProd>(opi);
-        case 0x4c862000u: return cplx_ops<X87CSum, X87CProd>(opi);
-        default: return nullptr;
-    }
+    return table_fp<GetaccEntry, MakeGetacc>(raw, opi);
 }
 
 }  // namespace mpix

@@ -230,39 +230,44 @@ bool binding_ok(uint32_t op, uint32_t dt)
 
 extern "C" const char *mpix_build_info(void);
 
+// One family's entry of (op index, internal type): its fp, int and pair
+// tables in turn.
+template <class E>
+const E *entry_of(const E *(*fp)(int, int), const E *(*in)(int, int), const E *(*pair)(int, int),
+                  uint32_t opi, uint32_t it)
+{
+    const int raw = (int) (is_struct_pair(it) ? it : (it & 0xffffff00u));
+    const E *e = fp(raw, (int) opi);
+    if (!e)
+        e = in(raw, (int) opi);
+    if (!e)
+        e = pair(raw, (int) opi);
+    return e;
+}
+
 const Entry *gpu_entry(uint32_t opi, uint32_t it)
 {
-    uint32_t raw = is_struct_pair(it) ? it : (it & 0xffffff00u);
-    const Entry *e = mpix::lookup_fp((int) raw, (int) opi);
-    if (!e)
-        e = mpix::lookup_int((int) raw, (int) opi);
-    if (!e)
-        e = mpix::lookup_pair((int) raw, (int) opi);
-    return e;
+    return entry_of(mpix::lookup_fp, mpix::lookup_int, mpix::lookup_pair, opi, it);
 }
 
 // the fused get-accumulate's launchers of the same pair
 const mpix::GetaccEntry *getacc_entry(uint32_t opi, uint32_t it)
 {
-    uint32_t raw = is_struct_pair(it) ? it : (it & 0xffffff00u);
-    const mpix::GetaccEntry *e = mpix::lookup_getacc_fp((int) raw, (int) opi);
-    if (!e)
-        e = mpix::lookup_getacc_int((int) raw, (int) opi);
-    if (!e)
-        e = mpix::lookup_getacc_pair((int) raw, (int) opi);
-    return e;
+    return entry_of(mpix::lookup_getacc_fp, mpix::lookup_getacc_int, mpix::lookup_getacc_pair, opi,
+                    it);
 }
 
-// ... and of its iov-target form
+// ... of its iov-target form
 const mpix::GetaccIovEntry *getacc_iov_entry(uint32_t opi, uint32_t it)
 {
-    uint32_t raw = is_struct_pair(it) ? it : (it & 0xffffff00u);
-    const mpix::GetaccIovEntry *e = mpix::lookup_getacc_iov_fp((int) raw, (int) opi);
-    if (!e)
-        e = mpix::lookup_getacc_iov_int((int) raw, (int) opi);
-    if (!e)
-        e = mpix::lookup_getacc_iov_pair((int) raw, (int) opi);
-    return e;
+    return entry_of(mpix::lookup_getacc_iov_fp, mpix::lookup_getacc_iov_int,
+                    mpix::lookup_getacc_iov_pair, opi, it);
+}
+
+// ... and of the committed plans
+const mpix::PlanEntry *plan_entry(uint32_t opi, uint32_t it)
+{
+    return entry_of(mpix::lookup_plan_fp, mpix::lookup_plan_int, mpix::lookup_plan_pair, opi, it);
 }
 
 // ---------------------------------------------------------------- state
@@ -1682,6 +1687,28 @@ struct RunTable {
     std::vector<size_t> base, nrun;
 };
 
+// Group g of a run table, its arrays read from `tab`: the host table
+// (rt.tab.data()) or a device copy of it.
+struct ResidueGroup : mpix::RunGroup {
+    int64_t n;          // runs
+    uint64_t total;     // packed elements
+    int64_t resid;
+    ResidueGroup(const RunTable &rt, size_t g, const int64_t *tab)
+        : RunGroup(tab + rt.base[g], (int64_t) rt.nrun[g]), n((int64_t) rt.nrun[g]),
+          total((uint64_t) rt.gtotal[g]), resid(rt.resid[g]) {}
+};
+
+// Residues must keep the 4-byte (for smaller types, the extent's) alignment
+// the element loads need.
+bool residues_aligned(const std::vector<Run> &runs, int64_t e)
+{
+    const int64_t align = e < 4 ? e : 4;
+    for (const Run &r : runs)
+        if ((((r.off % e) + e) % e) % align)
+            return false;
+    return true;
+}
+
 void group_runs(const std::vector<Run> &runs, int64_t e, RunTable *rt)
 {
     std::vector<std::vector<size_t>> groups;
@@ -1776,11 +1803,27 @@ int upload_runs(const RunTable &rt, hipStream_t s, DevState::IovSlot **slot)
                                   s));
 }
 
+// Group the runs, upload their table on `s`, launch every residue group
+// through launch(group) (a hipError_t) and record the event the slot is owed.
+template <class F>
+int launch_groups(const std::vector<Run> &runs, int64_t e, hipStream_t s, F launch)
+{
+    RunTable rt;
+    group_runs(runs, e, &rt);
+    DevState::IovSlot *sl = nullptr;
+    int rc = upload_runs(rt, s, &sl);
+    for (size_t g = 0; g < rt.resid.size() && rc == MPIX_REDOP_SUCCESS; ++g)
+        rc = hip_err(launch(ResidueGroup(rt, g, sl->tab)));
+    if (!sl)
+        return rc;
+    const int rc2 = hip_err(hipEventRecord(sl->done, s));
+    return rc ? rc : rc2;
+}
+
 // Enqueue a list of runs on `s`.  Runs are split by their offset modulo the
 // extent so each launch indexes inout in whole elements from one base
 // (inout + residue); the source offset table keeps the packed source in the
-// original run order.  Residues must keep the 4-byte (2-byte for 2-byte
-// types) alignment the element loads need.
+// original run order.
 int enqueue_runs(const void *inbuf, void *inoutbuf, const std::vector<Run> &runs, uint32_t dt,
                  uint32_t op, hipStream_t s)
 {
@@ -1804,10 +1847,9 @@ int enqueue_runs(const void *inbuf, void *inoutbuf, const std::vector<Run> &runs
         inbuf = pin;
         inoutbuf = (void *) pio;
     }
-    const int64_t e = (int64_t) ext, align = e < 4 ? e : 4;
-    for (const Run &r : runs)
-        if ((((r.off % e) + e) % e) % align)
-            return MPIX_REDOP_ERR_ARG;
+    const int64_t e = (int64_t) ext;
+    if (!residues_aligned(runs, e))
+        return MPIX_REDOP_ERR_ARG;
     uint32_t opi = op & 0xf;
     if (opi == 14)
         return MPIX_REDOP_SUCCESS;
@@ -1823,20 +1865,10 @@ int enqueue_runs(const void *inbuf, void *inoutbuf, const std::vector<Run> &runs
     const Entry *en = gpu_entry(opi, it);
     if (!en)
         return MPIX_REDOP_ERR_TYPE;
-    RunTable rt;
-    group_runs(runs, e, &rt);
-    DevState::IovSlot *sl = nullptr;
-    rc = upload_runs(rt, s, &sl);
-    for (size_t g = 0; g < rt.resid.size() && rc == MPIX_REDOP_SUCCESS; ++g) {
-        const int64_t n = (int64_t) rt.nrun[g];
-        const int64_t *t = sl->tab + rt.base[g];
-        rc = hip_err(en->iov(inbuf, (char *) inoutbuf + rt.resid[g], t, t + n, t + 2 * n + 1, n,
-                             (uint64_t) rt.gtotal[g], params(), launch_cfg(), s));
-    }
-    if (!sl)
-        return rc;
-    int rc2 = hip_err(hipEventRecord(sl->done, s));
-    return rc ? rc : rc2;
+    return launch_groups(runs, e, s, [&](const ResidueGroup &g) {
+        return en->iov(inbuf, (char *) inoutbuf + g.resid, g.seg_off, g.prefix, g.src_off, g.n,
+                       g.total, params(), launch_cfg(), s);
+    });
 }
 
 }  // namespace
@@ -2525,10 +2557,9 @@ static int getacc_runs(const void *origin, void *result, void *target,
     const bool reads_origin = opi != 14;    // MPI_NO_OP: origin may be NULL
     if (no_buffer(result) || no_buffer(target) || (reads_origin && no_buffer(origin)))
         return MPIX_REDOP_ERR_BUFFER;
-    const int64_t e = (int64_t) ext, align = e < 4 ? e : 4;
-    for (const Run &r : runs)
-        if ((((r.off % e) + e) % e) % align)
-            return MPIX_REDOP_ERR_ARG;
+    const int64_t e = (int64_t) ext;
+    if (!residues_aligned(runs, e))
+        return MPIX_REDOP_ERR_ARG;
     if (over || hi - lo >= span_cap || total * ext >= (uint64_t) span_cap)
         return MPIX_REDOP_ERR_COUNT;
     const uint64_t packed = total * ext, span = (uint64_t) (hi - lo);
@@ -2547,27 +2578,15 @@ static int getacc_runs(const void *origin, void *result, void *target,
         return MPIX_REDOP_ERR_BUFFER;
     PairMap pm{0, 0};
     (void) padded_pair(it, &pm);
-    RunTable rt;
-    group_runs(runs, e, &rt);
-    DevState::IovSlot *sl = nullptr;
-    rc = upload_runs(rt, s, &sl);
-    for (size_t g = 0; g < rt.resid.size() && rc == MPIX_REDOP_SUCCESS; ++g) {
-        const int64_t n = (int64_t) rt.nrun[g];
-        const int64_t *t = sl->tab + rt.base[g];
-        void *tg = (char *) pt + rt.resid[g];
+    return launch_groups(runs, e, s, [&](const ResidueGroup &g) {
+        void *tg = (char *) pt + g.resid;
         if (en)
-            rc = hip_err(en->iov(po, (void *) pr, tg, t, t + n, t + 2 * n + 1, n,
-                                 (uint64_t) rt.gtotal[g], params(), launch_cfg(), s));
-        else
-            rc = hip_err(mpix::launch_getacc_iov_copy(opi == 13, (uint32_t) ext, pm.value_bytes,
-                                                      pm.loc_off, po, (void *) pr, tg, t, t + n,
-                                                      t + 2 * n + 1, n, (uint64_t) rt.gtotal[g],
-                                                      launch_cfg(), s));
-    }
-    if (!sl)
-        return rc;
-    const int rc2 = hip_err(hipEventRecord(sl->done, s));
-    return rc ? rc : rc2;
+            return en->iov(po, (void *) pr, tg, g.seg_off, g.prefix, g.src_off, g.n, g.total,
+                           params(), launch_cfg(), s);
+        return mpix::launch_getacc_iov_copy(opi == 13, (uint32_t) ext, pm.value_bytes, pm.loc_off,
+                                            po, (void *) pr, tg, g.seg_off, g.prefix, g.src_off,
+                                            g.n, g.total, launch_cfg(), s);
+    });
 }
 
 int MPIX_Get_accumulate_local_iov_async(const void *origin, void *result, void *target,
@@ -2624,7 +2643,7 @@ static int plan_build(std::vector<Run> &runs, uint32_t it, uint64_t ext, MPIX_Io
     // total elements and the bounding byte range as the iov entries find them
     // (getacc_runs): zero-length runs aside; sums through 128 bits, since
     // n * ext may not fit 64 for a table about to be refused
-    const int64_t e = (int64_t) ext, align = e < 4 ? e : 4;
+    const int64_t e = (int64_t) ext;
     const uint64_t cap = ((uint64_t) 1 << 56) / ext;
     const __int128 span_cap = (__int128) 1 << 56;
     uint64_t total = 0;
@@ -2648,9 +2667,8 @@ static int plan_build(std::vector<Run> &runs, uint32_t it, uint64_t ext, MPIX_Io
     // a table of zero elements is a valid plan whatever its offsets are, as
     // the entries succeed on it; otherwise every run's residue counts
     if (over || total != 0) {
-        for (const Run &r : runs)
-            if ((((r.off % e) + e) % e) % align)
-                return MPIX_REDOP_ERR_ARG;
+        if (!residues_aligned(runs, e))
+            return MPIX_REDOP_ERR_ARG;
         if (over || hi - lo >= span_cap || (__int128) total * e >= span_cap)
             return MPIX_REDOP_ERR_COUNT;
     }
@@ -2692,17 +2710,16 @@ static int plan_build(std::vector<Run> &runs, uint32_t it, uint64_t ext, MPIX_Io
         }
         p->tile.resize(need);
         for (size_t g = 0; g < ng; ++g) {
-            const int64_t n = (int64_t) p->rt.nrun[g];
-            const int64_t *prefix = p->rt.tab.data() + p->rt.base[g] + n;
+            const ResidueGroup gr(p->rt, g, p->rt.tab.data());
             int32_t *tl = p->tile.data() + p->tile_base[g];
-            const uint64_t ntile = ((uint64_t) p->rt.gtotal[g] + 255) / 256;
+            const uint64_t ntile = (gr.total + 255) / 256;
             int64_t s = 0;
             for (uint64_t t = 0; t < ntile; ++t) {
-                while (s + 1 < n && (uint64_t) prefix[s + 1] <= t * 256)
+                while (s + 1 < gr.n && (uint64_t) gr.prefix[s + 1] <= t * 256)
                     ++s;
                 tl[t] = (int32_t) s;
             }
-            tl[ntile] = (int32_t) (n - 1);
+            tl[ntile] = (int32_t) (gr.n - 1);
         }
         p->table_bytes = p->rt.tab.size() * sizeof(int64_t) + p->tile.size() * sizeof(int32_t);
     }
@@ -2836,17 +2853,6 @@ int MPIX_Iov_plan_free(MPIX_Iov_plan *plan)
     return set_err(rc);
 }
 
-static const mpix::PlanEntry *plan_entry(uint32_t opi, uint32_t it)
-{
-    const uint32_t raw = is_struct_pair(it) ? it : (it & 0xffffff00u);
-    const mpix::PlanEntry *e = mpix::lookup_plan_fp((int) raw, (int) opi);
-    if (!e)
-        e = mpix::lookup_plan_int((int) raw, (int) opi);
-    if (!e)
-        e = mpix::lookup_plan_pair((int) raw, (int) opi);
-    return e;
-}
-
 // Checks 1-6 of the plan-taking entries (mpix_redop.h), none of which needs a
 // device.  origin NULL-able: the fetch form under MPI_NO_OP.  *n = 0 when there
 // is nothing to do.
@@ -2871,8 +2877,8 @@ static int plan_validate(const void *origin, const void *result, const void *tar
                           (fetch && ranges_overlap(origin, packed, result, packed)))))
         return MPIX_REDOP_ERR_BUFFER;
     // a plan of one run launches through gpu_entry / getacc_entry instead: every
-    // table is instantiated over the same (type, op) list, so one lookup answers
-    // for all (tests/test_plan_cpu.py compares the error classes pair by pair)
+    // family is built from the one (type, op) table (redop_tables.h), so one
+    // lookup answers for all
     if (opi < 13 && !plan_entry(opi, p->it))
         return MPIX_REDOP_ERR_TYPE;     // a legal pair without a kernel
     *n = p->total;
@@ -2926,18 +2932,19 @@ static int plan_enqueue(const void *origin, void *result, void *target, MPIX_Iov
     const int32_t *tiles = (const int32_t *) (tab + p->rt.tab.size() * sizeof(int64_t));
     const int mode = !fetch ? 2 : (opi == 13 ? 1 : 0);
     for (size_t g = 0; g < p->rt.resid.size() && rc == MPIX_REDOP_SUCCESS; ++g) {
-        const int64_t n = (int64_t) p->rt.nrun[g];
-        const int64_t *t = (const int64_t *) tab + p->rt.base[g];
+        const ResidueGroup gr(p->rt, g, (const int64_t *) tab);
+        const int64_t *t = gr.seg_off;      // the group's whole table
         const int32_t *tl = tiles + p->tile_base[g];
-        void *tg = (char *) pt + p->rt.resid[g];
-        const uint64_t gt = (uint64_t) p->rt.gtotal[g];
+        void *tg = (char *) pt + gr.resid;
         if (!en)
             rc = hip_err(mpix::launch_plan_copy(mode, (uint32_t) p->ext, pm.value_bytes, pm.loc_off,
-                                                po, (void *) pr, tg, t, tl, n, gt, launch_cfg(), s));
+                                                po, (void *) pr, tg, t, tl, gr.n, gr.total,
+                                                launch_cfg(), s));
         else if (fetch)
-            rc = hip_err(en->getacc(po, (void *) pr, tg, t, tl, n, gt, params(), launch_cfg(), s));
+            rc = hip_err(en->getacc(po, (void *) pr, tg, t, tl, gr.n, gr.total, params(),
+                                    launch_cfg(), s));
         else
-            rc = hip_err(en->reduce(po, tg, t, tl, n, gt, params(), launch_cfg(), s));
+            rc = hip_err(en->reduce(po, tg, t, tl, gr.n, gr.total, params(), launch_cfg(), s));
     }
     return rc;
 }

@@ -88,15 +88,26 @@ constexpr int kMaxMultiInputs = 16;
 
 // Each instantiation unit resolves (raw internal type, op index) to an Entry
 // or returns nullptr.  raw = handle & 0xffffff00 for builtins; struct pair
-// handles 0x8c00000k are passed unchanged.
+// handles 0x8c00000k are passed unchanged.  The four kernel families below
+// (Entry, GetaccEntry, GetaccIovEntry, PlanEntry) are built from the one
+// (type, op) table of redop_tables.h, each in instantiation units of its own
+// that compile side by side, so a pair has an entry in all of them or in none.
 const Entry *lookup_int(int raw, int opi);
 const Entry *lookup_fp(int raw, int opi);
 const Entry *lookup_pair(int raw, int opi);
 
+// One residue group's run table as it lies in memory, on the host or on the
+// device: [seg_off n][prefix n+1][src_off n] -- each run's element offset into
+// the target, the packed elements of the group before it (prefix[n] = the
+// group's total), and its first element's index in the packed operands.
+struct RunGroup {
+    const int64_t *seg_off, *prefix, *src_off;
+    RunGroup(const int64_t *tab, int64_t n)
+        : seg_off(tab), prefix(tab + n), src_off(tab + 2 * n + 1) {}
+};
+
 // The fused get-accumulate (MPIX_Get_accumulate_local*): result = target,
-// target = target OP origin in one pass.  A table of its own, built in its own
-// instantiation units (inst_getacc_*.hip) so they compile beside the
-// reduction's; a pair has a GetaccEntry exactly when it has an Entry.
+// target = target OP origin in one pass (inst_getacc_*.hip).
 struct GetaccEntry {
     hipError_t (*contig)(const void *origin, void *result, void *target, uint64_t count,
                          const Params &, const LaunchCfg &, hipStream_t);
@@ -111,9 +122,7 @@ const GetaccEntry *lookup_getacc_pair(int raw, int opi);
 
 // The fetch form over an iov target (MPIX_Get_accumulate_local_iov[ec]_async):
 // Entry::iov's run table with the packed result beside the packed origin, both
-// indexed by d_src_off.  A table and units of its own again
-// (inst_getacc_iov_*.hip); a pair has a GetaccIovEntry exactly when it has a
-// GetaccEntry.
+// indexed by d_src_off (inst_getacc_iov_*.hip).
 struct GetaccIovEntry {
     hipError_t (*iov)(const void *origin, void *result, void *target, const int64_t *d_seg_off,
                       const int64_t *d_prefix, const int64_t *d_src_off, int64_t nseg,
@@ -137,11 +146,9 @@ hipError_t launch_getacc_iov_copy(bool replace, uint32_t extent, uint32_t value_
                                   const LaunchCfg &, hipStream_t);
 
 // The reduce and the fetch form over a committed plan (MPIX_Iov_plan,
-// MPIX_*_local_plan*): one residue group's resident table d_tab =
-// [seg_off nseg][prefix nseg+1][src_off nseg] and its per-tile index d_tile
-// (the run holding packed index 256 t, closed by nseg - 1).  A table and units
-// of its own once more (inst_plan_*.hip); a pair has a PlanEntry exactly when
-// it has a GetaccIovEntry.
+// MPIX_*_local_plan*): one residue group's resident table d_tab (RunGroup's
+// layout) and its per-tile index d_tile (the run holding packed index 256 t,
+// closed by nseg - 1) (inst_plan_*.hip).
 struct PlanEntry {
     hipError_t (*reduce)(const void *in, void *io, const int64_t *d_tab, const int32_t *d_tile,
                          int64_t nseg, uint64_t total, const Params &, const LaunchCfg &,

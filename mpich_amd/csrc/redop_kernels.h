@@ -947,8 +947,86 @@ k_vector_s2(const typename C::unit *__restrict__ in, typename C::unit *__restric
 // source elements start at src_off[s] of the packed source (runs are
 // consumed in order, so src_off is the running prefix unless the host split
 // the runs by alignment class).  prefix[s] = elements before run s in this
-// launch (prefix[nseg] = total).  Thread per element, run found by binary
-// search over the L2-resident prefix table.
+// launch (prefix[nseg] = total).  Thread per packed element; every kernel over
+// such a table is one of the two loops below with a way to find the lane's run
+// and what to do with target element t and packed element p.
+
+// last s in [lo, hi] with prefix[s] <= j
+__device__ __forceinline__ int64_t iov_search(const int64_t *__restrict__ prefix, int64_t lo,
+                                              int64_t hi, uint64_t j)
+{
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if ((uint64_t) prefix[mid] <= j)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    return lo;
+}
+
+// The run of packed index j < total = prefix[nseg]: LOOKUP 0 = a binary search
+// per lane over the whole prefix table; 1 = one wave-uniform search for the
+// wave's first index, which serves every lane when the wave's last index lies
+// in the same run, else the lanes search from that run on.  Every caller runs
+// 256-thread blocks over j = block * 256 + thread + i * (nblk * 256), so the
+// active lanes of a wave hold consecutive indices from j & ~63.
+template <int LOOKUP>
+__device__ __forceinline__ int64_t iov_run(const int64_t *__restrict__ prefix, int64_t nseg,
+                                           uint64_t j, uint64_t total)
+{
+    if constexpr (LOOKUP == 0) {
+        return iov_search(prefix, 0, nseg - 1, j);
+    } else {
+        const uint64_t w = j & ~(uint64_t) 63;
+        const uint64_t first =
+            ((uint64_t) __builtin_amdgcn_readfirstlane((uint32_t) (w >> 32)) << 32) |
+            __builtin_amdgcn_readfirstlane((uint32_t) w);
+        const uint64_t last = first + 63 < total ? first + 63 : total - 1;
+        const int64_t s = iov_search(prefix, 0, nseg - 1, first);       // wave-uniform
+        if ((uint64_t) prefix[s + 1] > last)
+            return s;
+        return iov_search(prefix, s, nseg - 1, j);
+    }
+}
+
+// The run of packed index j = 256 t + thread < total of a committed plan
+// (below): LOOKUP 0 = the per-tile index, 1 = iov_run<1>.
+template <int LOOKUP>
+__device__ __forceinline__ int64_t plan_run(const int64_t *__restrict__ prefix,
+                                            const int32_t *__restrict__ tile, int64_t nseg,
+                                            uint64_t t, uint64_t j, uint64_t total)
+{
+    if constexpr (LOOKUP == 0) {
+        const int64_t lo = tile[t], hi = tile[t + 1];       // block-uniform
+        if (lo == hi)
+            return lo;
+        return iov_search(prefix, lo, hi, j);
+    } else {
+        return iov_run<1>(prefix, nseg, j, total);
+    }
+}
+
+// Packed index j of run s: target element t, packed element p
+struct RunAt {
+    int64_t t, p;
+};
+__device__ __forceinline__ RunAt run_at(const int64_t *__restrict__ seg_off,
+                                        const int64_t *__restrict__ prefix,
+                                        const int64_t *__restrict__ src_off, int64_t s, uint64_t j)
+{
+    const int64_t k = (int64_t) (j - (uint64_t) prefix[s]);
+    return RunAt{seg_off[s] + k, src_off[s] + k};
+}
+
+// Every kernel over a table runs 256-thread blocks (launch_runs) in one of two
+// loops: a grid-stride over the packed indices with iov_run, or a tile of 256
+// per iteration with plan_run, whose tile index is then block-uniform.  The
+// loop and its element stay written out in each kernel: behind a function
+// boundary (a functor, a lambda, a helper) the compiler narrows the load and the
+// store of the padded 32-byte pair (MPI_LONG_DOUBLE_INT) to its members, and
+// those partial stores measured 1-3 % slower.
+
 template <class C>
 __global__ void __launch_bounds__(256)
 k_iov(const typename C::unit *__restrict__ in, typename C::unit *__restrict__ io,
@@ -956,19 +1034,10 @@ k_iov(const typename C::unit *__restrict__ in, typename C::unit *__restrict__ io
       const int64_t *__restrict__ src_off, int64_t nseg, uint64_t total, Params prm,
       uint32_t nblk)
 {
-    const uint64_t stride = (uint64_t) nblk * 256;        // 256-thread blocks (launch_iov)
+    const uint64_t stride = (uint64_t) nblk * 256;
     for (uint64_t j = (uint64_t) blockIdx.x * 256 + threadIdx.x; j < total; j += stride) {
-        int64_t lo = 0, hi = nseg - 1;
-        while (lo < hi) {               // last s with prefix[s] <= j
-            int64_t mid = (lo + hi + 1) >> 1;
-            if ((uint64_t) prefix[mid] <= j)
-                lo = mid;
-            else
-                hi = mid - 1;
-        }
-        const int64_t k = (int64_t) (j - (uint64_t) prefix[lo]);
-        const int64_t t = seg_off[lo] + k;
-        io[t] = C::apply(io[t], in[src_off[lo] + k], prm);
+        const RunAt r = run_at(seg_off, prefix, src_off, iov_run<0>(prefix, nseg, j, total), j);
+        io[r.t] = C::apply(io[r.t], in[r.p], prm);
     }
 }
 
@@ -1258,18 +1327,40 @@ hipError_t launch_vector(const void *in, void *io, uint64_t count, uint64_t bl, 
     return hipGetLastError();
 }
 
+// The launch of every kernel over a run table: nothing
+// for an empty table, else 256-thread blocks of four packed elements per
+// thread, striding beyond the grid cap; the grid size is the kernel's last
+// argument after `args`.
+template <class K, class... A>
+hipError_t launch_runs(K kernel, int64_t nseg, uint64_t total, const LaunchCfg &cfg, hipStream_t s,
+                       A... args)
+{
+    if (total == 0 || nseg == 0)
+        return hipSuccess;
+    const unsigned grid = grid_for(256ull * 4, total, cfg.max_grid, 256);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, args..., grid);
+    return hipGetLastError();
+}
+
+// ... and its Params: these kernels signal no completion word and run the full
+// C::apply (no fixup words)
+inline Params run_params(const Params &prm)
+{
+    Params p = prm;
+    p.done = nullptr;
+    p.fixup = nullptr;
+    return p;
+}
+
 template <class C>
 hipError_t launch_iov(const void *in, void *io, const int64_t *d_seg_off, const int64_t *d_prefix,
                       const int64_t *d_src_off, int64_t nseg, uint64_t total, const Params &prm,
                       const LaunchCfg &cfg, hipStream_t s)
 {
     using T = typename C::unit;
-    if (total == 0 || nseg == 0)
-        return hipSuccess;
-    unsigned grid = grid_for(256ull * 4, total, cfg.max_grid, 256);
-    hipLaunchKernelGGL((k_iov<C>), dim3(grid), dim3(256), 0, s, static_cast<const T *>(in),
-                       static_cast<T *>(io), d_seg_off, d_prefix, d_src_off, nseg, total, prm, grid);
-    return hipGetLastError();
+    return launch_runs(k_iov<C>, nseg, total, cfg, s, static_cast<const T *>(in),
+                       static_cast<T *>(io), d_seg_off, d_prefix, d_src_off, nseg, total,
+                       run_params(prm));
 }
 
 // k independent contiguous combines (no operand range of one overlapping a
@@ -1610,10 +1701,12 @@ hipError_t launch_getacc_vector(const void *in, void *res, void *io, uint64_t co
     return hipGetLastError();
 }
 
-template <class C> constexpr GetaccEntry getacc_entry()
-{
-    return GetaccEntry{&launch_getacc<C>, &launch_getacc_vector<C>};
-}
+template <class C> struct MakeGetacc {
+    static constexpr GetaccEntry get()
+    {
+        return GetaccEntry{&launch_getacc<C>, &launch_getacc_vector<C>};
+    }
+};
 
 // ---------------------------------------------------------------------------
 // The fetch form over an iov target (MPIX_Get_accumulate_local_iov[ec]_async):
@@ -1622,48 +1715,28 @@ template <class C> constexpr GetaccEntry getacc_entry()
 // target element is seg_off[s] + k and the packed element of BOTH origin and
 // result is src_off[s] + k (the call's run order, not this residue group's).
 
-// How a lane finds its run: 0 = a binary search per lane over the whole
-// prefix table (k_iov's); 1 = one wave-uniform search for the wave's first
-// index, which serves every lane when the wave's last index lies in the same
-// run, else the lanes search from that run on.  The choice is measured
-// (tools/getacc_rows.py iov, DESIGN.md "Fused get-accumulate").
+// How a lane finds its run (iov_run): k_iov's search per lane, or the
+// wave-uniform one.  The choice is measured (tools/getacc_rows.py iov,
+// DESIGN.md "Fused get-accumulate").
 #ifndef MPIX_GETACC_IOV_LOOKUP
 #define MPIX_GETACC_IOV_LOOKUP 1
 #endif
 
-// last s in [lo, hi] with prefix[s] <= j
-__device__ __forceinline__ int64_t iov_search(const int64_t *__restrict__ prefix, int64_t lo,
-                                              int64_t hi, uint64_t j)
+// MPI_NO_OP and MPI_REPLACE as type-map copies: GATHER the target's element
+// into the packed result, SCATTER the packed origin's over the target.  T is
+// the unit's body (a raw unit of its extent, or the padded pair), not a
+// combiner.
+template <class T, bool GATHER, bool SCATTER>
+__device__ __forceinline__ void typemap_copy(const T *__restrict__ in, T *__restrict__ res,
+                                             T *__restrict__ io, const RunAt &r)
 {
-    while (lo < hi) {
-        const int64_t mid = (lo + hi + 1) >> 1;
-        if ((uint64_t) prefix[mid] <= j)
-            lo = mid;
-        else
-            hi = mid - 1;
+    if constexpr (GATHER) {
+        const T a = io[r.t];
+        FetchStore<T>::st(res + r.p, a);
     }
-    return lo;
-}
-
-// The run of packed index j < total = prefix[nseg].  Every caller runs
-// 256-thread blocks over j = block * 256 + thread + i * (nblk * 256), so the
-// active lanes of a wave hold consecutive indices from j & ~63.
-template <int LOOKUP>
-__device__ __forceinline__ int64_t iov_run(const int64_t *__restrict__ prefix, int64_t nseg,
-                                           uint64_t j, uint64_t total)
-{
-    if constexpr (LOOKUP == 0) {
-        return iov_search(prefix, 0, nseg - 1, j);
-    } else {
-        const uint64_t w = j & ~(uint64_t) 63;
-        const uint64_t first =
-            ((uint64_t) __builtin_amdgcn_readfirstlane((uint32_t) (w >> 32)) << 32) |
-            __builtin_amdgcn_readfirstlane((uint32_t) w);
-        const uint64_t last = first + 63 < total ? first + 63 : total - 1;
-        const int64_t s = iov_search(prefix, 0, nseg - 1, first);       // wave-uniform
-        if ((uint64_t) prefix[s + 1] > last)
-            return s;
-        return iov_search(prefix, s, nseg - 1, j);
+    if constexpr (SCATTER) {
+        const T b = in[r.p];
+        FetchStore<T>::st(io + r.t, b);
     }
 }
 
@@ -1679,21 +1752,16 @@ k_getacc_iov(const typename C::unit *__restrict__ in, typename C::unit *__restri
              uint64_t total, Params prm, uint32_t nblk)
 {
     using T = typename C::unit;
-    const uint64_t stride = (uint64_t) nblk * 256;        // 256-thread blocks (launch_getacc_iov)
+    const uint64_t stride = (uint64_t) nblk * 256;
     for (uint64_t j = (uint64_t) blockIdx.x * 256 + threadIdx.x; j < total; j += stride) {
-        const int64_t s = iov_run<MPIX_GETACC_IOV_LOOKUP>(prefix, nseg, j, total);
-        const int64_t k = (int64_t) (j - (uint64_t) prefix[s]);
-        const int64_t t = seg_off[s] + k, p = src_off[s] + k;
-        const T a = io[t];
-        FetchStore<T>::st(res + p, a);
-        io[t] = C::apply(a, in[p], prm);
+        const RunAt r = run_at(seg_off, prefix, src_off, iov_run<MPIX_GETACC_IOV_LOOKUP>(prefix, nseg, j, total), j);
+        const T a = io[r.t];
+        FetchStore<T>::st(res + r.p, a);
+        io[r.t] = C::apply(a, in[r.p], prm);
     }
 }
 
-// MPI_NO_OP and MPI_REPLACE over the same table, one launch per residue group
-// however many runs it has: gather the runs' type map into the packed result
-// and, REPLACE, scatter the origin's type map over them.  T is the unit's body
-// (a raw unit of its extent, or the padded pair), not a combiner.
+// one launch per residue group however many runs it has
 template <class T, bool REPLACE>
 __global__ void __launch_bounds__(256)
 k_getacc_iov_copy(const T *__restrict__ in, T *__restrict__ res, T *__restrict__ io,
@@ -1702,15 +1770,8 @@ k_getacc_iov_copy(const T *__restrict__ in, T *__restrict__ res, T *__restrict__
 {
     const uint64_t stride = (uint64_t) nblk * 256;
     for (uint64_t j = (uint64_t) blockIdx.x * 256 + threadIdx.x; j < total; j += stride) {
-        const int64_t s = iov_run<MPIX_GETACC_IOV_LOOKUP>(prefix, nseg, j, total);
-        const int64_t k = (int64_t) (j - (uint64_t) prefix[s]);
-        const int64_t t = seg_off[s] + k, p = src_off[s] + k;
-        const T a = io[t];
-        FetchStore<T>::st(res + p, a);
-        if constexpr (REPLACE) {
-            const T b = in[p];
-            FetchStore<T>::st(io + t, b);
-        }
+        const RunAt r = run_at(seg_off, prefix, src_off, iov_run<MPIX_GETACC_IOV_LOOKUP>(prefix, nseg, j, total), j);
+        typemap_copy<T, true, REPLACE>(in, res, io, r);
     }
 }
 
@@ -1720,16 +1781,9 @@ hipError_t launch_getacc_iov(const void *in, void *res, void *io, const int64_t 
                              uint64_t total, const Params &prm, const LaunchCfg &cfg, hipStream_t s)
 {
     using T = typename C::unit;
-    if (total == 0 || nseg == 0)
-        return hipSuccess;
-    Params p = prm;
-    p.done = nullptr;
-    p.fixup = nullptr;
-    const unsigned grid = grid_for(256ull * 4, total, cfg.max_grid, 256);
-    hipLaunchKernelGGL((k_getacc_iov<C>), dim3(grid), dim3(256), 0, s, static_cast<const T *>(in),
+    return launch_runs(k_getacc_iov<C>, nseg, total, cfg, s, static_cast<const T *>(in),
                        static_cast<T *>(res), static_cast<T *>(io), d_seg_off, d_prefix, d_src_off,
-                       nseg, total, p, grid);
-    return hipGetLastError();
+                       nseg, total, run_params(prm));
 }
 
 template <class T>
@@ -1738,24 +1792,49 @@ hipError_t launch_getacc_iov_copy_as(bool replace, const void *in, void *res, vo
                                      const int64_t *d_src_off, int64_t nseg, uint64_t total,
                                      const LaunchCfg &cfg, hipStream_t s)
 {
-    if (total == 0 || nseg == 0)
-        return hipSuccess;
-    const unsigned grid = grid_for(256ull * 4, total, cfg.max_grid, 256);
-    if (replace)
-        hipLaunchKernelGGL((k_getacc_iov_copy<T, true>), dim3(grid), dim3(256), 0, s,
-                           static_cast<const T *>(in), static_cast<T *>(res), static_cast<T *>(io),
-                           d_seg_off, d_prefix, d_src_off, nseg, total, grid);
-    else
-        hipLaunchKernelGGL((k_getacc_iov_copy<T, false>), dim3(grid), dim3(256), 0, s,
-                           static_cast<const T *>(in), static_cast<T *>(res), static_cast<T *>(io),
-                           d_seg_off, d_prefix, d_src_off, nseg, total, grid);
-    return hipGetLastError();
+    return launch_runs(replace ? k_getacc_iov_copy<T, true> : k_getacc_iov_copy<T, false>, nseg,
+                       total, cfg, s, static_cast<const T *>(in), static_cast<T *>(res),
+                       static_cast<T *>(io), d_seg_off, d_prefix, d_src_off, nseg, total);
 }
 
-template <class C> constexpr GetaccIovEntry getacc_iov_entry()
+// The unit body of a type map of `extent` bytes: the whole extent
+// (value_bytes == 0) or a value of value_bytes at 0 and an int at loc_off (the
+// padded pairs, copied member by member through FetchStore).  f(T{}) for that
+// body T; hipErrorInvalidValue for a layout without a kernel.
+namespace {
+// a 32-byte unit (the x87 / binary128 complex types) at the 16-byte alignment
+// of their combiners' units
+struct alignas(16) Raw32 {
+    v4u lo, hi;
+};
+}  // namespace
+
+template <class F>
+hipError_t with_copy_body(uint32_t extent, uint32_t value_bytes, uint32_t loc_off, F f)
 {
-    return GetaccIovEntry{&launch_getacc_iov<C>};
+    if (value_bytes) {
+        if (extent == 16 && value_bytes == 8 && loc_off == 8)
+            return f(DoubleIntBody{});      // MPI_LONG_INT has the same map
+        if (extent == 8 && value_bytes == 2 && loc_off == 4)
+            return f(ShortInt{});
+        if (extent == 32 && value_bytes == 16 && loc_off == 16)
+            return f(LongDoubleInt{});
+        return hipErrorInvalidValue;
+    }
+    switch (extent) {
+        case 1: return f(uint8_t{});
+        case 2: return f(RawOf<2>::type{});
+        case 4: return f(RawOf<4>::type{});
+        case 8: return f(RawOf<8>::type{});
+        case 16: return f(RawOf<16>::type{});
+        case 32: return f(Raw32{});
+        default: return hipErrorInvalidValue;
+    }
 }
+
+template <class C> struct MakeGetaccIov {
+    static constexpr GetaccIovEntry get() { return GetaccIovEntry{&launch_getacc_iov<C>}; }
+};
 
 // ---------------------------------------------------------------------------
 // Committed iov plans (MPIX_Iov_plan_*, MPIX_*_local_plan*): the run table of
@@ -1767,30 +1846,14 @@ template <class C> constexpr GetaccIovEntry getacc_iov_entry()
 // [tile[t], tile[t + 1]]: no search when the two are equal, else a search of
 // `prefix` between them only.
 
-// How a lane finds its run: 0 = the per-tile index; 1 = iov_run<1>'s
+// How a lane finds its run (plan_run): the per-tile index, or iov_run<1>'s
 // wave-uniform search over the whole prefix table.  The choice is measured
 // (tools/getacc_rows.py plan, DESIGN.md "Committed iov plans").
 #ifndef MPIX_PLAN_LOOKUP
 #define MPIX_PLAN_LOOKUP 0
 #endif
 
-// The run of packed index j = 256 t + thread < total.
-template <int LOOKUP>
-__device__ __forceinline__ int64_t plan_run(const int64_t *__restrict__ prefix,
-                                            const int32_t *__restrict__ tile, int64_t nseg,
-                                            uint64_t t, uint64_t j, uint64_t total)
-{
-    if constexpr (LOOKUP == 0) {
-        const int64_t lo = tile[t], hi = tile[t + 1];       // block-uniform
-        if (lo == hi)
-            return lo;
-        return iov_search(prefix, lo, hi, j);
-    } else {
-        return iov_run<1>(prefix, nseg, j, total);
-    }
-}
-
-// k_iov's body: inout element = inout element OP packed source element.
+// k_iov's element: inout element = inout element OP packed source element.
 template <class C>
 __global__ void __launch_bounds__(256)
 k_plan_reduce(const typename C::unit *__restrict__ in, typename C::unit *__restrict__ io,
@@ -1798,20 +1861,17 @@ k_plan_reduce(const typename C::unit *__restrict__ in, typename C::unit *__restr
               const int64_t *__restrict__ src_off, const int32_t *__restrict__ tile, int64_t nseg,
               uint64_t total, Params prm, uint32_t nblk)
 {
-    for (uint64_t t = blockIdx.x; t * 256 < total; t += nblk) {     // 256-thread blocks
+    for (uint64_t t = blockIdx.x; t * 256 < total; t += nblk) {
         const uint64_t j = t * 256 + threadIdx.x;
         if (j >= total)
             break;
-        const int64_t s = plan_run<MPIX_PLAN_LOOKUP>(prefix, tile, nseg, t, j, total);
-        const int64_t k = (int64_t) (j - (uint64_t) prefix[s]);
-        const int64_t e = seg_off[s] + k;
-        io[e] = C::apply(io[e], in[src_off[s] + k], prm);
+        const RunAt r = run_at(seg_off, prefix, src_off,
+                               plan_run<MPIX_PLAN_LOOKUP>(prefix, tile, nseg, t, j, total), j);
+        io[r.t] = C::apply(io[r.t], in[r.p], prm);
     }
 }
 
-// k_getacc_iov's body: the old target element goes to the result through
-// FetchStore (type map only) and is combined; the full C::apply, no fixup
-// words, no shared state.
+// k_getacc_iov's element
 template <class C>
 __global__ void __launch_bounds__(256)
 k_plan_getacc(const typename C::unit *__restrict__ in, typename C::unit *__restrict__ res,
@@ -1825,12 +1885,11 @@ k_plan_getacc(const typename C::unit *__restrict__ in, typename C::unit *__restr
         const uint64_t j = t * 256 + threadIdx.x;
         if (j >= total)
             break;
-        const int64_t s = plan_run<MPIX_PLAN_LOOKUP>(prefix, tile, nseg, t, j, total);
-        const int64_t k = (int64_t) (j - (uint64_t) prefix[s]);
-        const int64_t e = seg_off[s] + k, p = src_off[s] + k;
-        const T a = io[e];
-        FetchStore<T>::st(res + p, a);
-        io[e] = C::apply(a, in[p], prm);
+        const RunAt r = run_at(seg_off, prefix, src_off,
+                               plan_run<MPIX_PLAN_LOOKUP>(prefix, tile, nseg, t, j, total), j);
+        const T a = io[r.t];
+        FetchStore<T>::st(res + r.p, a);
+        io[r.t] = C::apply(a, in[r.p], prm);
     }
 }
 
@@ -1850,39 +1909,24 @@ k_plan_copy(const T *__restrict__ in, T *__restrict__ res, T *__restrict__ io,
         const uint64_t j = t * 256 + threadIdx.x;
         if (j >= total)
             break;
-        const int64_t s = plan_run<MPIX_PLAN_LOOKUP>(prefix, tile, nseg, t, j, total);
-        const int64_t k = (int64_t) (j - (uint64_t) prefix[s]);
-        const int64_t e = seg_off[s] + k, p = src_off[s] + k;
-        if constexpr (MODE != kPlanScatter) {
-            const T a = io[e];
-            FetchStore<T>::st(res + p, a);
-        }
-        if constexpr (MODE != kPlanGather) {
-            const T b = in[p];
-            FetchStore<T>::st(io + e, b);
-        }
+        const RunAt r = run_at(seg_off, prefix, src_off,
+                               plan_run<MPIX_PLAN_LOOKUP>(prefix, tile, nseg, t, j, total), j);
+        typemap_copy<T, MODE != kPlanScatter, MODE != kPlanGather>(in, res, io, r);
     }
 }
 
-// One residue group's device table as the host lays it out (MPIX_Iov_plan_s in
-// redop_capi.cpp: its RunTable, group g from base[g]): [seg_off n][prefix n+1]
-// [src_off n]; the group's tile index is passed beside it (tile_base[g]).
+// One residue group's device table as the host lays it out (RunGroup,
+// redop_dispatch.h); the group's tile index is passed beside it.
 template <class C>
 hipError_t launch_plan_reduce(const void *in, void *io, const int64_t *d_tab,
                               const int32_t *d_tile, int64_t nseg, uint64_t total,
                               const Params &prm, const LaunchCfg &cfg, hipStream_t s)
 {
     using T = typename C::unit;
-    if (total == 0 || nseg == 0)
-        return hipSuccess;
-    Params p = prm;
-    p.done = nullptr;
-    p.fixup = nullptr;
-    const unsigned grid = grid_for(256ull * 4, total, cfg.max_grid, 256);
-    hipLaunchKernelGGL((k_plan_reduce<C>), dim3(grid), dim3(256), 0, s, static_cast<const T *>(in),
-                       static_cast<T *>(io), d_tab, d_tab + nseg, d_tab + 2 * nseg + 1, d_tile,
-                       nseg, total, p, grid);
-    return hipGetLastError();
+    const RunGroup g(d_tab, nseg);
+    return launch_runs(k_plan_reduce<C>, nseg, total, cfg, s, static_cast<const T *>(in),
+                       static_cast<T *>(io), g.seg_off, g.prefix, g.src_off, d_tile, nseg, total,
+                       run_params(prm));
 }
 
 template <class C>
@@ -1891,16 +1935,10 @@ hipError_t launch_plan_getacc(const void *in, void *res, void *io, const int64_t
                               const Params &prm, const LaunchCfg &cfg, hipStream_t s)
 {
     using T = typename C::unit;
-    if (total == 0 || nseg == 0)
-        return hipSuccess;
-    Params p = prm;
-    p.done = nullptr;
-    p.fixup = nullptr;
-    const unsigned grid = grid_for(256ull * 4, total, cfg.max_grid, 256);
-    hipLaunchKernelGGL((k_plan_getacc<C>), dim3(grid), dim3(256), 0, s, static_cast<const T *>(in),
-                       static_cast<T *>(res), static_cast<T *>(io), d_tab, d_tab + nseg,
-                       d_tab + 2 * nseg + 1, d_tile, nseg, total, p, grid);
-    return hipGetLastError();
+    const RunGroup g(d_tab, nseg);
+    return launch_runs(k_plan_getacc<C>, nseg, total, cfg, s, static_cast<const T *>(in),
+                       static_cast<T *>(res), static_cast<T *>(io), g.seg_off, g.prefix, g.src_off,
+                       d_tile, nseg, total, run_params(prm));
 }
 
 template <class T>
@@ -1908,27 +1946,24 @@ hipError_t launch_plan_copy_as(int mode, const void *in, void *res, void *io, co
                                const int32_t *d_tile, int64_t nseg, uint64_t total,
                                const LaunchCfg &cfg, hipStream_t s)
 {
-    if (total == 0 || nseg == 0)
-        return hipSuccess;
-    const unsigned grid = grid_for(256ull * 4, total, cfg.max_grid, 256);
-#define MPIX_PLAN_COPY(MODE)                                                                    \
-    hipLaunchKernelGGL((k_plan_copy<T, MODE>), dim3(grid), dim3(256), 0, s,                     \
-                       static_cast<const T *>(in), static_cast<T *>(res), static_cast<T *>(io), \
-                       d_tab, d_tab + nseg, d_tab + 2 * nseg + 1, d_tile, nseg, total, grid)
-    switch (mode) {
-        case kPlanGather: MPIX_PLAN_COPY(kPlanGather); break;
-        case kPlanSwap: MPIX_PLAN_COPY(kPlanSwap); break;
-        case kPlanScatter: MPIX_PLAN_COPY(kPlanScatter); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef MPIX_PLAN_COPY
-    return hipGetLastError();
+    auto kernel = mode == kPlanGather    ? k_plan_copy<T, kPlanGather>
+                  : mode == kPlanSwap    ? k_plan_copy<T, kPlanSwap>
+                  : mode == kPlanScatter ? k_plan_copy<T, kPlanScatter>
+                                         : nullptr;
+    if (!kernel)
+        return hipErrorInvalidValue;
+    const RunGroup g(d_tab, nseg);
+    return launch_runs(kernel, nseg, total, cfg, s, static_cast<const T *>(in),
+                       static_cast<T *>(res), static_cast<T *>(io), g.seg_off, g.prefix, g.src_off,
+                       d_tile, nseg, total);
 }
 
-template <class C> constexpr PlanEntry plan_entry()
-{
-    return PlanEntry{&launch_plan_reduce<C>, &launch_plan_getacc<C>};
-}
+template <class C> struct MakePlan {
+    static constexpr PlanEntry get()
+    {
+        return PlanEntry{&launch_plan_reduce<C>, &launch_plan_getacc<C>};
+    }
+};
 
 // ---------------------------------------------------------------------------
 // MPI_Compare_and_swap's local step on one element of 1, 2, 4, 8 or 16 bytes
@@ -1949,10 +1984,14 @@ k_cas(const void *origin, const void *compare, void *result, void *target)
         *static_cast<UU *>(target) = o;
 }
 
-template <class C> constexpr Entry entry()
-{
-    return Entry{&launch_contig<C>, &launch_vector<C>, &launch_multi<C>, &launch_iov<C>,
-                 &launch_tree<C>, &launch_batch<C>};
-}
+// The launchers of combiner C as one table entry of each family: the makers
+// redop_tables.h builds the (type, op) tables over.
+template <class C> struct MakeEntry {
+    static constexpr Entry get()
+    {
+        return Entry{&launch_contig<C>, &launch_vector<C>, &launch_multi<C>, &launch_iov<C>,
+                     &launch_tree<C>, &launch_batch<C>};
+    }
+};
 
 }  // namespace mpix

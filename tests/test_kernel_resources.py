@@ -65,6 +65,36 @@ def test_no_kernel_uses_scratch(kernels):
     assert not spilled, spilled[:5]
 
 
+def test_every_kernel_family_is_built_over_the_same_combiners():
+    """the reduction, the fused get-accumulate, its iov form and the committed
+    plans instantiate one (type, op) table (redop_tables.h): per unit, the
+    combiner template arguments of one kernel of each family are the same list"""
+    if not (os.path.exists(OBJDUMP) and os.path.exists(READELF)):
+        pytest.skip('ROCm llvm tools not found')
+    params = 'EvPKNT_4unitE'     # every one of these kernels takes `const typename C::unit *` first
+    families = [('inst_%s.o', '_ZN4mpix5k_iovI'),
+                ('inst_getacc_%s.o', '_ZN4mpix13k_getacc_elemI'),
+                ('inst_getacc_iov_%s.o', '_ZN4mpix12k_getacc_iovI'),
+                ('inst_plan_%s.o', '_ZN4mpix13k_plan_reduceI'),
+                ('inst_plan_%s.o', '_ZN4mpix13k_plan_getaccI')]
+    objs = {f % u for f, _ in families for u in ('int', 'fp', 'pair')}
+    if not all(os.path.exists(os.path.join(BUILD, o)) for o in objs):
+        pytest.skip('library objects not built (run __graft_entry__.build())')
+    names = {o: [k[0] for k in _kernels(os.path.join(BUILD, o))] for o in objs}
+    total = 0
+    for u in ('int', 'fp', 'pair'):
+        lists = []
+        for f, prefix in families:
+            ns = [n for n in names[f % u] if n.startswith(prefix)]
+            assert ns and all(params in n for n in ns), (f % u, prefix)
+            lists.append(sorted(n[len(prefix):n.index(params)] for n in ns))
+        assert len(set(lists[0])) == len(lists[0]), u
+        for (f, prefix), l in zip(families[1:], lists[1:]):
+            assert l == lists[0], (f % u, prefix, sorted(set(l) ^ set(lists[0]))[:5])
+        total += len(lists[0])
+    assert total >= 100
+
+
 def test_contiguous_kernels_under_the_vgpr_cap(kernels):
     contig = [(n, v) for n, v, _, _ in kernels if n.startswith('_ZN4mpix8k_contig')]
     assert len(contig) >= 200

@@ -442,6 +442,78 @@ int MPIX_Compare_and_swap_local_async(const void *origin, const void *compare, v
 int MPIX_Compare_and_swap_local(const void *origin, const void *compare, void *result,
                                 void *target, MPIX_Datatype datatype);
 
+/* ---- element-atomic accumulate, fetch-and-op and compare-and-swap ----
+ * MPI's guarantee for concurrent accumulates to one target element with the
+ * same predefined type, without a lock around the call: for every i < count
+ *     target[i] = target[i] OP origin[i]
+ * is ONE atomic read-modify-write at device scope on the 32- or 64-bit word
+ * that holds the element, and in the fetch form result[i] is the value the
+ * element had before that step.  The reference gets this from one mutex on its
+ * shared-memory path (posix_rma.h:361-378) and from hardware atomics on its
+ * network path where the (type, op) table allows (ofi_rma.h:67-132, 777-790);
+ * this is the second way.
+ *
+ * The step is atomic with respect to every other call of these entries (any
+ * op, on a type of the same extent), from any stream or thread, and from any
+ * process that has the target mapped on the same device (MPIX_Ipc_open).
+ * It is NOT atomic against the other, non-atomic entries of this header
+ * (plain loads and stores: keep the window's lock between the two kinds), and
+ * NOT across devices: a peer GPU's or the host's accesses to the target are
+ * outside device scope.  The calls stay stream-ordered: the async forms
+ * allocate nothing, record no event and wait for nothing.
+ *
+ * The combine is that of MPIX_Get_accumulate_local_async (target in the inout
+ * role, origin in the in role): a caller that runs alone gets the same target
+ * and result bits, NaNs, signed zeros, denormals, the bf16 store rule, Annex G
+ * and pair padding included.  MPI_NO_OP is an atomic fetch (origin not read,
+ * may be NULL; in the non-fetch form it does nothing); MPI_REPLACE an atomic
+ * exchange, in the non-fetch form an atomic store per element; MPIX_EQUAL is
+ * MPI_ERR_OP.
+ *
+ * Checks, all before any device work and in this order: those of
+ * MPIX_Get_accumulate_local_async (count < 0, MPIX_EQUAL, a non-builtin op, an
+ * unknown type, an illegal pair, count == 0 succeeds without looking at a
+ * pointer, the 2^56-byte cap, NULL / MPI_IN_PLACE buffers, any overlap among
+ * the byte ranges), then MPI_ERR_TYPE for a pair MPIX_Accumulate_atomic_is_
+ * supported declines -- no kernel (bf16 other than SUM) or an extent of 16 or
+ * 32 bytes (__int128, DOUBLE_INT, LONG_INT, the 2 x 64-bit pairs, double
+ * complex, every long double / binary128 type): keep the lock and the
+ * non-atomic entry for those -- then MPI_ERR_BUFFER for a target that is not
+ * aligned to its extent.  Then, MPI_ERR_BUFFER as well: a target that is not
+ * device memory of the stream's device (page-locked host memory, managed
+ * memory, a peer device).  Origin and result are operands a kernel on `stream`
+ * can dereference, element-aligned.  The sync forms run on the calling
+ * thread's library stream and return when target and result are visible. */
+int MPIX_Accumulate_local_atomic_async(const void *origin, void *target, MPIX_Aint count,
+                                       MPIX_Datatype datatype, MPIX_Op op, void *stream);
+int MPIX_Accumulate_local_atomic(const void *origin, void *target, MPIX_Aint count,
+                                 MPIX_Datatype datatype, MPIX_Op op);
+int MPIX_Get_accumulate_local_atomic_async(const void *origin, void *result, void *target,
+                                           MPIX_Aint count, MPIX_Datatype datatype, MPIX_Op op,
+                                           void *stream);
+int MPIX_Get_accumulate_local_atomic(const void *origin, void *result, void *target,
+                                     MPIX_Aint count, MPIX_Datatype datatype, MPIX_Op op);
+
+/* MPIX_Compare_and_swap_local as one device-scope compare-exchange, atomic as
+ * above (also against the atomic accumulates on the same element).  The type
+ * rule and the checks are MPIX_Compare_and_swap_local's; then the 16-byte
+ * types are MPI_ERR_TYPE (no 128-bit atomic), a target not aligned to its size
+ * or not device memory of the stream's device MPI_ERR_BUFFER.  origin, compare
+ * and result need no alignment. */
+int MPIX_Compare_and_swap_local_atomic_async(const void *origin, const void *compare,
+                                             void *result, void *target, MPIX_Datatype datatype,
+                                             void *stream);
+int MPIX_Compare_and_swap_local_atomic(const void *origin, const void *compare, void *result,
+                                       void *target, MPIX_Datatype datatype);
+
+/* 1 exactly when the atomic entries take (op, datatype): the pair is legal, it
+ * has a kernel, and the internal type's extent is 1, 2, 4 or 8 bytes; with
+ * MPI_OP_NULL it asks about MPIX_Compare_and_swap_local_atomic (the type is
+ * RMA-atomic and at most 8 bytes).  MPIX_EQUAL is 0.  No HIP call: query once
+ * per window and (type, op), as MPIDI_OFI_query_acc_atomic_support does
+ * (max_count == 0 <-> 0 here). */
+int MPIX_Accumulate_atomic_is_supported(MPIX_Op op, MPIX_Datatype datatype);
+
 /* Multi-input form: equivalent to `ninputs` MPIX_Reduce_local calls
  *   for k = 0 .. ninputs-1:  inoutbuf = inoutbuf OP inbufs[k]
  * in that order (same association, same bits) but done in one pass over

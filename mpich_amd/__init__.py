@@ -18,7 +18,10 @@ def __getattr__(name):
         import importlib
         return importlib.import_module('.' + name, __name__)
     # the committed iov plans of mpich_amd.redop, under the package's own name
-    if name in ('IovPlan', 'reduce_local_plan', 'get_accumulate_local_plan'):
+    # and the element-atomic entries
+    if name in ('IovPlan', 'reduce_local_plan', 'get_accumulate_local_plan',
+                'accumulate_local_atomic', 'get_accumulate_local_atomic',
+                'compare_and_swap_local_atomic', 'accumulate_atomic_is_supported'):
         import importlib
         return getattr(importlib.import_module('.redop', __name__), name)
     raise AttributeError(name)

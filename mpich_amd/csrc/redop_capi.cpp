@@ -3071,6 +3071,251 @@ int MPIX_Compare_and_swap_local(const void *origin, const void *compare, void *r
     return set_err(rc ? rc : rc2);
 }
 
+// ------------------------------------- element-atomic accumulate
+// The counterpart of the reference handing an accumulate to hardware atomics
+// where its (type, op) table allows (ofi_rma.h:67-132, MPIDI_OFI_query_acc_
+// atomic_support): device-scope read-modify-write / compare-exchange per
+// element on the word that holds it (redop_atomic.h).
+static const mpix::AtomicEntry *atomic_entry(uint32_t opi, uint32_t it)
+{
+    return entry_of(mpix::lookup_acc_atomic_fp, mpix::lookup_acc_atomic_int,
+                    mpix::lookup_acc_atomic_pair, opi, it);
+}
+
+static bool atomic_extent(uint64_t ext) { return ext == 1 || ext == 2 || ext == 4 || ext == 8; }
+
+// MPIR_Type_is_rma_atomic (rmatypeutil.c:18-30), cas_validate's rule
+static bool rma_atomic_type(uint32_t it)
+{
+    if (it == kNull || !is_builtin(it) || !(it & 0x800000u) || (it & 0x400000u))
+        return false;
+    const uint32_t kind = it & 0x0f0000u;
+    return kind == 0x010000u || kind == 0x020000u;
+}
+
+// The pair alone, no HIP call: legal, a kernel in the table, and an extent
+// the device has an atomic for.  MPI_OP_NULL asks about compare-and-swap.
+static int atomic_supported(uint32_t op, uint32_t it)
+{
+    if (it == kNull || !atomic_extent(extent_of(it)))
+        return 0;
+    if (op == 0x18000000u)
+        return rma_atomic_type(it) ? 1 : 0;
+    if (!is_builtin_op(op) || (op & 0xf) == 15 || !internal_ok(op, it))
+        return 0;
+    const uint32_t opi = op & 0xf;
+    if (opi == 13 || opi == 14)
+        return 1;
+    const mpix::AtomicEntry *e = atomic_entry(opi, it);
+    return (e && e->acc && e->getacc) ? 1 : 0;
+}
+
+// getacc_validate's checks in its order for a contiguous target (fetch: the
+// call has a result), then the two of this family: a pair without an atomic
+// kernel (MPI_ERR_TYPE) and a target not aligned to its extent
+// (MPI_ERR_BUFFER).  No device work.
+static int atomic_validate(const void *origin, const void *result, const void *target,
+                           MPIX_Aint count, uint32_t dt, uint32_t op, bool fetch, uint32_t *it,
+                           uint64_t *ext, uint64_t *n)
+{
+    *n = 0;
+    if (count < 0)
+        return MPIX_REDOP_ERR_COUNT;
+    if (is_builtin_op(op) && (op & 0xf) == 15)
+        return MPIX_REDOP_ERR_OP;       // MPIX_EQUAL is no accumulate op
+    int rc = validate(nullptr, nullptr, 0, dt, op, it, ext);
+    if (rc != MPIX_REDOP_SUCCESS || count == 0)
+        return rc;
+    const uint64_t c = (uint64_t) count;
+    if (c > ((uint64_t) 1 << 56) / *ext)
+        return MPIX_REDOP_ERR_COUNT;
+    const bool reads_origin = (op & 0xf) != 14;     // MPI_NO_OP: origin may be NULL
+    if ((fetch && no_buffer(result)) || no_buffer(target) || (reads_origin && no_buffer(origin)))
+        return MPIX_REDOP_ERR_BUFFER;
+    const uint64_t bytes = c * *ext;
+    if ((fetch && ranges_overlap(result, bytes, target, bytes)) ||
+        (reads_origin && (ranges_overlap(origin, bytes, target, bytes) ||
+                          (fetch && ranges_overlap(origin, bytes, result, bytes)))))
+        return MPIX_REDOP_ERR_BUFFER;
+    if (!atomic_supported(op, *it))
+        return MPIX_REDOP_ERR_TYPE;     // no kernel, or no atomic of this extent
+    if ((uintptr_t) target % *ext)
+        return MPIX_REDOP_ERR_BUFFER;   // the element would straddle its word
+    *n = c;
+    return MPIX_REDOP_SUCCESS;
+}
+
+// Device-scope atomics cover device memory of the launching device only: not
+// page-locked host memory, not managed memory, not a peer's.
+static bool atomic_target_ok(const void *target, int dev)
+{
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, target) != hipSuccess) {
+        (void) hipGetLastError();
+        return false;
+    }
+    return a.type == hipMemoryTypeDevice && a.device == dev;
+}
+
+static int atomic_enqueue(const void *origin, void *result, void *target, uint64_t count,
+                          uint32_t it, uint64_t ext, uint32_t op, bool fetch, hipStream_t s)
+{
+    const uint32_t opi = op & 0xf;
+    int launch = stream_device(s);
+    if (!atomic_target_ok(target, launch))
+        return MPIX_REDOP_ERR_BUFFER;
+    const void *po = origin, *pr = result;
+    bool zc = false;
+    if ((fetch && !reachable(result, s, &launch, &pr, &zc)) ||
+        (opi != 14 && !reachable(origin, s, &launch, &po, &zc)))
+        return MPIX_REDOP_ERR_BUFFER;
+    if (opi == 14 && !fetch)
+        return MPIX_REDOP_SUCCESS;
+    const LaunchCfg cfg = launch_cfg(zc);
+    if (opi == 13 || opi == 14) {
+        PairMap pm{0, 0};
+        (void) padded_pair(it, &pm);
+        return hip_err(mpix::launch_atomic_copy(opi == 14 ? 0 : fetch ? 1 : 2, (uint32_t) ext,
+                                                pm.value_bytes, pm.loc_off, po, (void *) pr, target,
+                                                count, cfg, s));
+    }
+    const mpix::AtomicEntry *e = atomic_entry(opi, it);
+    if (!e || !e->acc || !e->getacc)
+        return MPIX_REDOP_ERR_TYPE;
+    if (fetch)
+        return hip_err(e->getacc(po, (void *) pr, target, count, params(), cfg, s));
+    return hip_err(e->acc(po, target, count, params(), cfg, s));
+}
+
+static int atomic_async(const void *origin, void *result, void *target, MPIX_Aint count,
+                        uint32_t dt, uint32_t op, bool fetch, hipStream_t s)
+{
+    uint32_t it;
+    uint64_t ext, n;
+    int rc = atomic_validate(origin, result, target, count, dt, op, fetch, &it, &ext, &n);
+    if (rc != MPIX_REDOP_SUCCESS || n == 0)
+        return rc;
+    return atomic_enqueue(origin, result, target, n, it, ext, op, fetch, s);
+}
+
+// the synchronous forms: the calling thread's library stream of the target's
+// device, and a wait on it
+extern "C++" {
+template <class F>
+static int atomic_on_library_stream(const void *target, F enqueue)
+{
+    int dev = 0;
+    const void *dp;
+    if (classify(target, &dev, &dp) != Where::Device)
+        return MPIX_REDOP_ERR_BUFFER;
+    DeviceGuard guard(dev);
+    DevState *d = dev_state(dev);
+    if (!d)
+        return MPIX_REDOP_ERR_OTHER;
+    const int rc = enqueue(d->s[0]);
+    const int rc2 = wait_stream(d, d->s[0]);
+    return rc ? rc : rc2;
+}
+}   // extern "C++"
+
+static int atomic_sync(const void *origin, void *result, void *target, MPIX_Aint count,
+                       uint32_t dt, uint32_t op, bool fetch)
+{
+    uint32_t it;
+    uint64_t ext, n;
+    int rc = atomic_validate(origin, result, target, count, dt, op, fetch, &it, &ext, &n);
+    if (rc != MPIX_REDOP_SUCCESS || n == 0)
+        return rc;
+    return atomic_on_library_stream(target, [&](hipStream_t s) {
+        return atomic_enqueue(origin, result, target, n, it, ext, op, fetch, s);
+    });
+}
+
+int MPIX_Accumulate_local_atomic_async(const void *origin, void *target, MPIX_Aint count,
+                                       MPIX_Datatype datatype, MPIX_Op op, void *stream)
+{
+    return set_err(atomic_async(origin, nullptr, target, count, (uint32_t) datatype, (uint32_t) op,
+                                false, (hipStream_t) stream));
+}
+
+int MPIX_Accumulate_local_atomic(const void *origin, void *target, MPIX_Aint count,
+                                 MPIX_Datatype datatype, MPIX_Op op)
+{
+    return set_err(atomic_sync(origin, nullptr, target, count, (uint32_t) datatype, (uint32_t) op,
+                               false));
+}
+
+int MPIX_Get_accumulate_local_atomic_async(const void *origin, void *result, void *target,
+                                           MPIX_Aint count, MPIX_Datatype datatype, MPIX_Op op,
+                                           void *stream)
+{
+    return set_err(atomic_async(origin, result, target, count, (uint32_t) datatype, (uint32_t) op,
+                                true, (hipStream_t) stream));
+}
+
+int MPIX_Get_accumulate_local_atomic(const void *origin, void *result, void *target,
+                                     MPIX_Aint count, MPIX_Datatype datatype, MPIX_Op op)
+{
+    return set_err(atomic_sync(origin, result, target, count, (uint32_t) datatype, (uint32_t) op,
+                               true));
+}
+
+// cas_validate's checks, then this family's: no 16-byte atomic (MPI_ERR_TYPE),
+// a target aligned to its size (MPI_ERR_BUFFER)
+static int cas_atomic_validate(const void *origin, const void *compare, const void *result,
+                               const void *target, uint32_t dt, uint32_t *size)
+{
+    int rc = cas_validate(origin, compare, result, target, dt, size);
+    if (rc != MPIX_REDOP_SUCCESS)
+        return rc;
+    if (!atomic_extent(*size))
+        return MPIX_REDOP_ERR_TYPE;
+    if ((uintptr_t) target % *size)
+        return MPIX_REDOP_ERR_BUFFER;
+    return MPIX_REDOP_SUCCESS;
+}
+
+static int cas_atomic_enqueue(const void *origin, const void *compare, void *result, void *target,
+                              uint32_t size, hipStream_t s)
+{
+    int launch = stream_device(s);
+    if (!atomic_target_ok(target, launch))
+        return MPIX_REDOP_ERR_BUFFER;
+    const void *po, *pc, *pr;
+    if (!reachable(origin, s, &launch, &po) || !reachable(compare, s, &launch, &pc) ||
+        !reachable(result, s, &launch, &pr))
+        return MPIX_REDOP_ERR_BUFFER;
+    return hip_err(mpix::launch_cas_atomic(size, po, pc, (void *) pr, target, s));
+}
+
+int MPIX_Compare_and_swap_local_atomic_async(const void *origin, const void *compare, void *result,
+                                             void *target, MPIX_Datatype datatype, void *stream)
+{
+    uint32_t size;
+    int rc = cas_atomic_validate(origin, compare, result, target, (uint32_t) datatype, &size);
+    if (rc != MPIX_REDOP_SUCCESS)
+        return set_err(rc);
+    return set_err(cas_atomic_enqueue(origin, compare, result, target, size,
+                                      (hipStream_t) stream));
+}
+
+int MPIX_Compare_and_swap_local_atomic(const void *origin, const void *compare, void *result,
+                                       void *target, MPIX_Datatype datatype)
+{
+    uint32_t size;
+    int rc = cas_atomic_validate(origin, compare, result, target, (uint32_t) datatype, &size);
+    if (rc != MPIX_REDOP_SUCCESS)
+        return set_err(rc);
+    return set_err(atomic_on_library_stream(target, [&](hipStream_t s) {
+        return cas_atomic_enqueue(origin, compare, result, target, size, s);
+    }));
+}
+
+int MPIX_Accumulate_atomic_is_supported(MPIX_Op op, MPIX_Datatype datatype)
+{
+    return atomic_supported((uint32_t) op, to_internal((uint32_t) datatype));
+}
+
 int MPIX_Reduce_local_multi_async(const void *const *inbufs, int ninputs, void *inoutbuf,
                                   MPIX_Aint count, MPIX_Datatype datatype, MPIX_Op op,
                                   void *stream)

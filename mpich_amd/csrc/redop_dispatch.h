@@ -88,10 +88,11 @@ constexpr int kMaxMultiInputs = 16;
 
 // Each instantiation unit resolves (raw internal type, op index) to an Entry
 // or returns nullptr.  raw = handle & 0xffffff00 for builtins; struct pair
-// handles 0x8c00000k are passed unchanged.  The four kernel families below
-// (Entry, GetaccEntry, GetaccIovEntry, PlanEntry) are built from the one
-// (type, op) table of redop_tables.h, each in instantiation units of its own
-// that compile side by side, so a pair has an entry in all of them or in none.
+// handles 0x8c00000k are passed unchanged.  The five kernel families below
+// (Entry, GetaccEntry, GetaccIovEntry, PlanEntry, AtomicEntry) are built from
+// the one (type, op) table of redop_tables.h, each in instantiation units of
+// its own that compile side by side, so a pair has an entry in all of them or
+// in none (AtomicEntry: with null launchers where the unit has no atomic).
 const Entry *lookup_int(int raw, int opi);
 const Entry *lookup_fp(int raw, int opi);
 const Entry *lookup_pair(int raw, int opi);
@@ -175,6 +176,39 @@ hipError_t launch_plan_copy(int mode, uint32_t extent, uint32_t value_bytes, uin
 // 16): *result = *target; if (*target == *compare) *target = *origin.
 hipError_t launch_cas(uint32_t size, const void *origin, const void *compare, void *result,
                       void *target, hipStream_t);
+
+// The element-atomic accumulate (MPIX_[Get_]accumulate_local_atomic*): every
+// element's target = target OP origin is one device-scope read-modify-write on
+// the 32- or 64-bit word that holds it; getacc also stores the element's value
+// before that step to the packed result (inst_acc_atomic_*.hip).  The target
+// is aligned to the unit.  Both launchers are null for a combiner whose unit
+// is wider than 8 bytes: there is no wider atomic, the entries decline it.
+struct AtomicEntry {
+    hipError_t (*acc)(const void *origin, void *target, uint64_t count, const Params &,
+                      const LaunchCfg &, hipStream_t);
+    hipError_t (*getacc)(const void *origin, void *result, void *target, uint64_t count,
+                         const Params &, const LaunchCfg &, hipStream_t);
+};
+
+const AtomicEntry *lookup_acc_atomic_int(int raw, int opi);
+const AtomicEntry *lookup_acc_atomic_fp(int raw, int opi);
+const AtomicEntry *lookup_acc_atomic_pair(int raw, int opi);
+
+// MPI_NO_OP and MPI_REPLACE of the atomic entries on elements of `extent`
+// bytes (1, 2, 4, 8) whose type map is the whole extent (value_bytes == 0) or
+// a value and an int (the padded 8-byte pair): mode 0 an atomic load per
+// element into the result, 1 an atomic exchange of the type map, 2 an atomic
+// store of it (no result).  hipErrorInvalidValue for a layout without a
+// kernel.  inst_acc_atomic_copy.hip.
+hipError_t launch_atomic_copy(int mode, uint32_t extent, uint32_t value_bytes, uint32_t loc_off,
+                              const void *origin, void *result, void *target, uint64_t count,
+                              const LaunchCfg &, hipStream_t);
+
+// MPI_Compare_and_swap as one device-scope compare-exchange on an aligned
+// integer element of `size` bytes (1, 2, 4, 8); origin, compare and result
+// need no alignment.  inst_acc_atomic_copy.hip.
+hipError_t launch_cas_atomic(uint32_t size, const void *origin, const void *compare, void *result,
+                             void *target, hipStream_t);
 
 // MPIX_EQUAL on an MPI_BYTE buffer of n >= 8 bytes (opequal.c:20-35)
 hipError_t launch_equal(const void *in, void *io, uint64_t n, hipStream_t s);

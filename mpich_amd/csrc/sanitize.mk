@@ -23,7 +23,9 @@ KOBJS = build/inst_int.o build/inst_fp.o build/inst_pair.o \
         build/inst_getacc_int.o build/inst_getacc_fp.o build/inst_getacc_pair.o \
         build/inst_getacc_iov_int.o build/inst_getacc_iov_fp.o build/inst_getacc_iov_pair.o \
         build/inst_getacc_copy.o \
-        build/inst_plan_int.o build/inst_plan_fp.o build/inst_plan_pair.o build/inst_plan_copy.o
+        build/inst_plan_int.o build/inst_plan_fp.o build/inst_plan_pair.o build/inst_plan_copy.o \
+        build/inst_acc_atomic_int.o build/inst_acc_atomic_fp.o build/inst_acc_atomic_pair.o \
+        build/inst_acc_atomic_copy.o
 
 all: $(OUT)/coll_host_sanitize
 
@@ -57,6 +59,13 @@ $(OUT)/coll_host_sanitize: ../../tests/c/coll_host_sanitize.c $(OUT)/libmpix_col
 # entries' device-free checks), a goal of its own:
 #   make -f sanitize.mk SAN=asan build/asan/plan_host_check
 $(OUT)/plan_host_check: ../../tests/c/plan_host_check.cpp $(OUT)/libmpix_redop.so
+	$(CXX) -std=c++17 -O1 -g -fno-omit-frame-pointer -Wall $(SANFLAGS) -D__HIP_PLATFORM_AMD__ \
+	    -I../../include -I/opt/rocm/include -o $@ $< -L$(OUT) -lmpix_redop \
+	    -Wl,-rpath,$(abspath $(OUT)) -Wl,-rpath,/opt/rocm/lib
+
+# the atomic entries' host side (the predicate and every device-free check):
+#   make -f sanitize.mk SAN=asan build/asan/acc_atomic_host_check
+$(OUT)/acc_atomic_host_check: ../../tests/c/acc_atomic_host_check.cpp $(OUT)/libmpix_redop.so
 	$(CXX) -std=c++17 -O1 -g -fno-omit-frame-pointer -Wall $(SANFLAGS) -D__HIP_PLATFORM_AMD__ \
 	    -I../../include -I/opt/rocm/include -o $@ $< -L$(OUT) -lmpix_redop \
 	    -Wl,-rpath,$(abspath $(OUT)) -Wl,-rpath,/opt/rocm/lib

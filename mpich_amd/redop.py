@@ -78,6 +78,13 @@ def lib():
             'MPIX_Get_accumulate_local_plan': ([vp, vp, vp, vp, i32], i32),
             'MPIX_Compare_and_swap_local': ([vp, vp, vp, vp, i32], i32),
             'MPIX_Compare_and_swap_local_async': ([vp, vp, vp, vp, i32, vp], i32),
+            'MPIX_Accumulate_local_atomic': ([vp, vp, aint, i32, i32], i32),
+            'MPIX_Accumulate_local_atomic_async': ([vp, vp, aint, i32, i32, vp], i32),
+            'MPIX_Get_accumulate_local_atomic': ([vp, vp, vp, aint, i32, i32], i32),
+            'MPIX_Get_accumulate_local_atomic_async': ([vp, vp, vp, aint, i32, i32, vp], i32),
+            'MPIX_Compare_and_swap_local_atomic': ([vp, vp, vp, vp, i32], i32),
+            'MPIX_Compare_and_swap_local_atomic_async': ([vp, vp, vp, vp, i32, vp], i32),
+            'MPIX_Accumulate_atomic_is_supported': ([i32, i32], i32),
             'MPIX_Redop_is_supported': ([i32, aint, i32], i32),
             'MPIX_Redop_is_supported_buffers': ([i32, aint, i32, vp, vp], i32),
             'MPIX_Redop_set_support': ([i32, aint, aint, aint], i32),
@@ -489,6 +496,51 @@ def compare_and_swap_local(origin, compare, result, target, datatype, stream=Non
     if sync:
         return lib().MPIX_Compare_and_swap_local(*args)
     return lib().MPIX_Compare_and_swap_local_async(*args, _stream_ptr(stream))
+
+
+def accumulate_local_atomic(origin, target, count, datatype, op, stream=None, sync=False):
+    """Element-atomic accumulate: every target[i] = target[i] OP origin[i] is
+    one device-scope read-modify-write, atomic against every other atomic call
+    on the target from any stream, thread or process on the device.  `origin`
+    may be None for MPI_NO_OP."""
+    _span_check(count, datatype, op, target, *([] if origin is None else [origin]))
+    args = (_addr(origin), _addr(target), count, H.as_c_int(datatype), H.as_c_int(op))
+    if sync:
+        return lib().MPIX_Accumulate_local_atomic(*args)
+    return lib().MPIX_Accumulate_local_atomic_async(*args, _stream_ptr(stream))
+
+
+def get_accumulate_local_atomic(origin, result, target, count, datatype, op, stream=None,
+                                sync=False):
+    """The fetch form: result[i] = the element's value before its atomic step
+    (MPI_Get_accumulate / MPI_Fetch_and_op without the window lock)."""
+    _span_check(count, datatype, op, result, target, *([] if origin is None else [origin]))
+    args = (_addr(origin), _addr(result), _addr(target), count, H.as_c_int(datatype),
+            H.as_c_int(op))
+    if sync:
+        return lib().MPIX_Get_accumulate_local_atomic(*args)
+    return lib().MPIX_Get_accumulate_local_atomic_async(*args, _stream_ptr(stream))
+
+
+def compare_and_swap_local_atomic(origin, compare, result, target, datatype, stream=None,
+                                  sync=False):
+    """compare_and_swap_local as one device-scope compare-exchange."""
+    ext = datatype_extent(datatype)
+    if ext > 0:
+        for b, what in ((origin, 'origin'), (compare, 'compare'), (result, 'result'),
+                        (target, 'target')):
+            if b is not None:
+                _range_check(b, 0, ext, what)
+    args = (_addr(origin), _addr(compare), _addr(result), _addr(target), H.as_c_int(datatype))
+    if sync:
+        return lib().MPIX_Compare_and_swap_local_atomic(*args)
+    return lib().MPIX_Compare_and_swap_local_atomic_async(*args, _stream_ptr(stream))
+
+
+def accumulate_atomic_is_supported(op, datatype):
+    """whether the atomic entries take (op, datatype); op = MPI_OP_NULL asks
+    about compare_and_swap_local_atomic.  CPU-only query."""
+    return bool(lib().MPIX_Accumulate_atomic_is_supported(H.as_c_int(op), H.as_c_int(datatype)))
 
 
 def reduce_local_multi_async(inbufs, inoutbuf, count, datatype, op, stream=None):

@@ -20,20 +20,20 @@ hipError_t atomic_copy_as(int mode, const void *origin, void *result, void *targ
 }
 }  // namespace
 
-hipError_t launch_atomic_copy(int mode, uint32_t extent, uint32_t value_bytes, uint32_t loc_off,
+hipError_t launch_atomic_copy(CopyMode mode, uint32_t extent, uint32_t value_bytes, uint32_t loc_off,
                               const void *origin, void *result, void *target, uint64_t count,
                               const LaunchCfg &cfg, hipStream_t s)
 {
     if (value_bytes) {
         if (extent == 8 && value_bytes == 2 && loc_off == 4)
-            return atomic_copy_as<ShortInt>(mode, origin, result, target, count, cfg, s);
+            return atomic_copy_as<ShortInt>((int) mode, origin, result, target, count, cfg, s);
         return hipErrorInvalidValue;
     }
     switch (extent) {
-        case 1: return atomic_copy_as<uint8_t>(mode, origin, result, target, count, cfg, s);
-        case 2: return atomic_copy_as<uint16_t>(mode, origin, result, target, count, cfg, s);
-        case 4: return atomic_copy_as<uint32_t>(mode, origin, result, target, count, cfg, s);
-        case 8: return atomic_copy_as<uint64_t>(mode, origin, result, target, count, cfg, s);
+        case 1: return atomic_copy_as<uint8_t>((int) mode, origin, result, target, count, cfg, s);
+        case 2: return atomic_copy_as<uint16_t>((int) mode, origin, result, target, count, cfg, s);
+        case 4: return atomic_copy_as<uint32_t>((int) mode, origin, result, target, count, cfg, s);
+        case 8: return atomic_copy_as<uint64_t>((int) mode, origin, result, target, count, cfg, s);
         default: return hipErrorInvalidValue;
     }
 }

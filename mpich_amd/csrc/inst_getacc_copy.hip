@@ -5,14 +5,14 @@
 
 namespace mpix {
 
-hipError_t launch_getacc_iov_copy(bool replace, uint32_t extent, uint32_t value_bytes,
+hipError_t launch_getacc_iov_copy(CopyMode mode, uint32_t extent, uint32_t value_bytes,
                                   uint32_t loc_off, const void *origin, void *result, void *target,
                                   const int64_t *d_seg_off, const int64_t *d_prefix,
                                   const int64_t *d_src_off, int64_t nseg, uint64_t total,
                                   const LaunchCfg &cfg, hipStream_t s)
 {
     return with_copy_body(extent, value_bytes, loc_off, [&](auto body) {
-        return launch_getacc_iov_copy_as<decltype(body)>(replace, origin, result, target,
+        return launch_getacc_iov_copy_as<decltype(body)>(mode != kCopyFetch, origin, result, target,
                                                          d_seg_off, d_prefix, d_src_off, nseg,
                                                          total, cfg, s);
     });

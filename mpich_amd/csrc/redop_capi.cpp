@@ -92,6 +92,8 @@ constexpr uint32_t kNull = 0x0c000000u;
 inline bool is_builtin(uint32_t h) { return (h >> 30) == 1u; }
 inline bool is_struct_pair(uint32_t h) { return (h & 0xffffff00u) == 0x8c000000u && (h & 0xff) < 5; }
 inline bool is_builtin_op(uint32_t op) { return (op >> 24) == 0x58u; }
+// The builtin ops that are no combiner, by index (op & 0xf), and MPI_OP_NULL.
+constexpr uint32_t kOpReplace = 13, kOpNoOp = 14, kOpEqual = 15, kOpNull = 0x18000000u;
 
 // MPIR_DATATYPE_REPLACE_BUILTIN (mpir_datatype.h:169-176)
 uint32_t to_internal(uint32_t dt)
@@ -174,6 +176,33 @@ int replace_rows(void *dst, size_t dpitch, const void *src, size_t spitch, uint6
     return rc;
 }
 
+// Type-map copy (MPIR_Localcopy) of `count` blocks of `bl` elements between
+// two buffers whose blocks start every dp / sp elements.
+int copy_blocks(void *dst, uint64_t dp, const void *src, uint64_t sp, uint64_t count,
+                       uint64_t bl, uint32_t it, uint64_t ext, hipStream_t s)
+{
+    if (dp == bl && sp == bl)
+        return replace_rows(dst, ext, src, ext, count * bl, it, ext, s);
+    PairMap pm;
+    if (!padded_pair(it, &pm))
+        return hip_err(hipMemcpy2DAsync(dst, dp * ext, src, sp * ext, bl * ext, count,
+                                        hipMemcpyDeviceToDevice, s));
+    int rc = MPIX_REDOP_SUCCESS;
+    if (bl <= count) {      // column k of every block
+        for (uint64_t k = 0; k < bl && rc == MPIX_REDOP_SUCCESS; ++k)
+            rc = replace_rows((char *) dst + k * ext, dp * ext, (const char *) src + k * ext,
+                              sp * ext, count, it, ext, s);
+    } else {                // block by block
+        for (uint64_t b = 0; b < count && rc == MPIX_REDOP_SUCCESS; ++b)
+            rc = replace_rows((char *) dst + b * dp * ext, ext, (const char *) src + b * sp * ext,
+                              ext, bl, it, ext, s);
+    }
+    return rc;
+}
+
+// the signed and the unsigned integers among the internal types' kinds (it & 0x0f0000u)
+inline bool integer_kind(uint32_t kind) { return kind == 0x010000u || kind == 0x020000u; }
+
 // MPIR_Internal_op_dt_check (mpir_datatype.h:870-933)
 bool internal_ok(uint32_t op, uint32_t it)
 {
@@ -182,20 +211,20 @@ bool internal_ok(uint32_t op, uint32_t it)
     uint32_t opi = op & 0xf;
     if (opi == 11 || opi == 12)
         return is_pairtype(it);
-    if (opi >= 13)
+    if (opi >= kOpReplace)
         return true;
     if (!is_builtin(it) || !(it & 0x800000u) || (it & 0x400000u))
         return false;
     uint32_t kind = it & 0x0f0000u;
     switch (opi) {
         case 1: case 2:
-            return kind == 0x010000u || kind == 0x020000u || kind == 0x030000u || kind == 0x050000u;
+            return integer_kind(kind) || kind == 0x030000u || kind == 0x050000u;
         case 3: case 4:
             return kind >= 0x010000u && kind <= 0x060000u;
         case 5: case 7: case 9:
-            return kind == 0x010000u || kind == 0x020000u || kind == 0x070000u;
+            return integer_kind(kind) || kind == 0x070000u;
         case 6: case 8: case 10:
-            return kind == 0x010000u || kind == 0x020000u;
+            return integer_kind(kind);
         default:
             return false;
     }
@@ -209,7 +238,7 @@ bool binding_ok(uint32_t op, uint32_t dt)
     uint32_t opi = op & 0xf;
     if (opi == 11 || opi == 12)
         return is_pairtype(to_internal(dt));
-    if (opi >= 13)
+    if (opi >= kOpReplace)
         return true;
     if (!is_builtin(dt))
         return false;
@@ -724,11 +753,19 @@ Where classify(const void *p, int *dev, const void **devptr)
     return Where::Pageable;
 }
 
+bool ranges_overlap(const void *a, uint64_t na, const void *b, uint64_t nb)
+{
+    const uintptr_t x = (uintptr_t) a, y = (uintptr_t) b;
+    return x < y + nb && y < x + na;
+}
+
 bool overlaps(const void *a, const void *b, uint64_t bytes)
 {
-    uintptr_t x = (uintptr_t) a, y = (uintptr_t) b;
-    return x < y + bytes && y < x + bytes;
+    return ranges_overlap(a, bytes, b, bytes);
 }
+
+// NULL or MPI_IN_PLACE
+bool no_buffer(const void *p) { return !p || p == (const void *) -1; }
 
 // Argument checks shared by every entry point: the binding-layer checks of
 // MPI_Reduce_local (binding_c.py:2774-2783: op/datatype legality, buffer
@@ -772,11 +809,11 @@ int enqueue(const void *in, void *io, uint64_t count, uint32_t it, uint64_t ext,
     if (signalled)
         *signalled = false;
     uint32_t opi = op & 0xf;
-    if (opi == 14)      // MPI_NO_OP
+    if (opi == kOpNoOp)
         return MPIX_REDOP_SUCCESS;
-    if (opi == 13)      // MPI_REPLACE = MPIR_Localcopy (op_fns.c:445-457)
+    if (opi == kOpReplace)      // = MPIR_Localcopy (op_fns.c:445-457)
         return replace_rows(io, ext, in, ext, count, it, ext, s);
-    if (opi == 15)      // MPIX_EQUAL, MPI_BYTE only (opequal.c:22-23)
+    if (opi == kOpEqual)        // MPI_BYTE only (opequal.c:22-23)
         return ((it & 0xffffff00u) == U8 && count >= 8)
             ? hip_err(mpix::launch_equal(in, io, count, s)) : MPIX_REDOP_ERR_TYPE;
     const Entry *e = gpu_entry(opi, it);
@@ -1837,7 +1874,7 @@ int enqueue_runs(const void *inbuf, void *inoutbuf, const std::vector<Run> &runs
         total += r.n;
     if (total == 0)
         return MPIX_REDOP_SUCCESS;
-    if (!inbuf || !inoutbuf || inbuf == (const void *) -1 || inoutbuf == (void *) -1)
+    if (no_buffer(inbuf) || no_buffer(inoutbuf))
         return MPIX_REDOP_ERR_BUFFER;
     {
         const void *pin, *pio;
@@ -1851,9 +1888,9 @@ int enqueue_runs(const void *inbuf, void *inoutbuf, const std::vector<Run> &runs
     if (!residues_aligned(runs, e))
         return MPIX_REDOP_ERR_ARG;
     uint32_t opi = op & 0xf;
-    if (opi == 14)
+    if (opi == kOpNoOp)
         return MPIX_REDOP_SUCCESS;
-    if (opi == 13) {    // REPLACE: one typemap copy per run
+    if (opi == kOpReplace) {    // one typemap copy per run
         int64_t src = 0;
         for (size_t k = 0; k < runs.size() && rc == MPIX_REDOP_SUCCESS; ++k) {
             rc = replace_rows((char *) inoutbuf + runs[k].off, ext,
@@ -1869,6 +1906,80 @@ int enqueue_runs(const void *inbuf, void *inoutbuf, const std::vector<Run> &runs
         return en->iov(inbuf, (char *) inoutbuf + g.resid, g.seg_off, g.prefix, g.src_off, g.n,
                        g.total, params(), launch_cfg(), s);
     });
+}
+
+// ------------------------------------------- the RMA-style entries' scaffolding
+// One operand rule, one placement and one synchronous tail for the fused
+// get-accumulate, its iov and plan forms and the element-atomic entries
+// (mpix_redop.h numbers the checks; every family calls these in that order).
+// fetch: the call has a result.  reads_origin: the origin is an operand (not
+// under the fetch forms' MPI_NO_OP, where it may be NULL).
+
+// The no-buffer check: an operand that is NULL or MPI_IN_PLACE.
+bool missing_operand(const void *origin, const void *result, const void *target, bool fetch,
+                     bool reads_origin)
+{
+    return (fetch && no_buffer(result)) || no_buffer(target) || (reads_origin && no_buffer(origin));
+}
+
+// The overlap check: the packed result and origin (`packed` bytes each)
+// against the target's bounding range (`span` bytes from target_lo) and
+// against each other.
+bool operands_overlap(const void *origin, const void *result, const void *target_lo,
+                      uint64_t packed, uint64_t span, bool fetch, bool reads_origin)
+{
+    return (fetch && ranges_overlap(result, packed, target_lo, span)) ||
+           (reads_origin && (ranges_overlap(origin, packed, target_lo, span) ||
+                             (fetch && ranges_overlap(origin, packed, result, packed))));
+}
+
+// The operands as a kernel on the stream dereferences them (reachable): filled
+// with the caller's pointers, translated in place -- result, target, origin,
+// in that order.  own_target: the caller has placed the target by a rule of
+// its own (atomic_target_ok) and set `launch`.
+struct Placed {
+    const void *origin, *result, *target;
+    int launch = -2;        // the stream's device, once a device operand asked for it
+    bool zc = false;        // an operand is page-locked host memory
+};
+
+bool place_operands(Placed *p, bool fetch, bool own_target, bool reads_origin, hipStream_t s)
+{
+    return (!fetch || reachable(p->result, s, &p->launch, &p->result, &p->zc)) &&
+           (own_target || reachable(p->target, s, &p->launch, &p->target, &p->zc)) &&
+           (!reads_origin || reachable(p->origin, s, &p->launch, &p->origin, &p->zc));
+}
+
+// The synchronous forms: a device-memory target, the calling thread's library
+// stream of that device, and a wait on it (no in-kernel completion word).
+template <class F>
+int on_library_stream(const void *target, F enqueue)
+{
+    int dev = 0;
+    const void *dp;
+    if (classify(target, &dev, &dp) != Where::Device)
+        return MPIX_REDOP_ERR_BUFFER;
+    DeviceGuard guard(dev);
+    DevState *d = dev_state(dev);
+    if (!d)
+        return MPIX_REDOP_ERR_OTHER;
+    const int rc = enqueue(d->s[0]);
+    const int rc2 = wait_stream(d, d->s[0]);
+    return rc ? rc : rc2;
+}
+
+// Validated arguments of either form of an entry: enqueue on the caller's
+// stream, or (sync) through on_library_stream.
+template <class F>
+int on_stream(bool sync, hipStream_t s, const void *target, F enqueue)
+{
+    return sync ? on_library_stream(target, enqueue) : enqueue(s);
+}
+
+// What the copy kernels of MPI_NO_OP / MPI_REPLACE do (redop_dispatch.h).
+mpix::CopyMode copy_mode(uint32_t opi, bool fetch)
+{
+    return !fetch ? mpix::kCopyStore : opi == kOpReplace ? mpix::kCopySwap : mpix::kCopyFetch;
 }
 
 }  // namespace
@@ -2061,8 +2172,8 @@ int MPIX_Reduce_local_batch_async(const void *const *inbufs, void *const *inoutb
         }
     }
     const uint32_t opi = (uint32_t) op & 0xf;
-    const Entry *e = (opi >= 13) ? nullptr : gpu_entry(opi, it);
-    if (opi < 13 && !e)
+    const Entry *e = (opi >= kOpReplace) ? nullptr : gpu_entry(opi, it);
+    if (opi < kOpReplace && !e)
         return set_err(MPIX_REDOP_ERR_TYPE);
     const void *pin[MPIX_BATCH_MAX];
     void *pio[MPIX_BATCH_MAX];
@@ -2116,8 +2227,8 @@ int MPIX_Reduce_local(const void *inbuf, void *inoutbuf, MPIX_Aint count, MPIX_D
     if (rc != MPIX_REDOP_SUCCESS || count == 0)
         return set_err(rc);
     uint32_t opi = (uint32_t) op & 0xf;
-    if (opi == 15 ? ((it & 0xffffff00u) != U8 || count < 8)
-                  : (opi != 13 && opi != 14 && !gpu_entry(opi, it)))
+    if (opi == kOpEqual ? ((it & 0xffffff00u) != U8 || count < 8)
+                        : (opi != kOpReplace && opi != kOpNoOp && !gpu_entry(opi, it)))
         return set_err(MPIX_REDOP_ERR_TYPE);
     launch_cfg();
     int din = -1, dio = -1, cur = 0;
@@ -2135,7 +2246,7 @@ int MPIX_Reduce_local(const void *inbuf, void *inoutbuf, MPIX_Aint count, MPIX_D
         // operands on two devices without peer access: the kernel runs where
         // inout lives and `in` is copied over in chunks (hipMemcpyPeerAsync);
         // MPIX_EQUAL's one header covers the whole message: copied whole
-        return set_err(opi == 15
+        return set_err(opi == kOpEqual
                            ? equal_whole(pin, (void *) pio, (uint64_t) count, false, false, dev, din)
                            : staged(pin, (void *) pio, (uint64_t) count, it, ext, (uint32_t) op,
                                     false, false, dev, din));
@@ -2148,7 +2259,7 @@ int MPIX_Reduce_local(const void *inbuf, void *inoutbuf, MPIX_Aint count, MPIX_D
         if (rc >= 0)
             return set_err(rc);
     }
-    if (opi == 15 && (in_stage || io_stage))
+    if (opi == kOpEqual && (in_stage || io_stage))
         // MPIX_EQUAL is one comparison over the whole buffer behind one
         // 8-byte header (opequal.c:20-35; MPIR_Reduce_equal: "we can't split
         // the message"), so it is never chunked
@@ -2194,11 +2305,10 @@ int MPIX_Reduce_local_vector_async(const void *inbuf, void *inoutbuf, MPIX_Aint 
     uint64_t n = (uint64_t) count * (uint64_t) blocklen;
     if (n == 0)
         return set_err(MPIX_REDOP_SUCCESS);
-    if (!inbuf || !inoutbuf || inbuf == (const void *) -1 || inoutbuf == (void *) -1)
+    if (no_buffer(inbuf) || no_buffer(inoutbuf))
         return set_err(MPIX_REDOP_ERR_BUFFER);
     uint64_t span = ((uint64_t) (count - 1) * (uint64_t) stride + (uint64_t) blocklen) * ext;
-    uintptr_t x = (uintptr_t) inbuf, y = (uintptr_t) inoutbuf;
-    if (x < y + span && y < x + n * ext)
+    if (ranges_overlap(inbuf, n * ext, inoutbuf, span))
         return set_err(MPIX_REDOP_ERR_BUFFER);
     {
         const void *pin, *pio;
@@ -2210,28 +2320,12 @@ int MPIX_Reduce_local_vector_async(const void *inbuf, void *inoutbuf, MPIX_Aint 
         inoutbuf = (void *) pio;
     }
     uint32_t opi = (uint32_t) op & 0xf;
-    if (opi == 14)
+    if (opi == kOpNoOp)
         return set_err(MPIX_REDOP_SUCCESS);
-    if (opi == 13) {
-        PairMap pm;
-        if (!padded_pair(it, &pm)) {
-            rc = hip_err(hipMemcpy2DAsync(inoutbuf, (size_t) stride * ext, inbuf,
-                                          (size_t) blocklen * ext, (size_t) blocklen * ext,
-                                          (size_t) count, hipMemcpyDeviceToDevice,
-                                          (hipStream_t) stream));
-        } else if (blocklen <= count) {     // column k of every block
-            for (MPIX_Aint k = 0; k < blocklen && rc == MPIX_REDOP_SUCCESS; ++k)
-                rc = replace_rows((char *) inoutbuf + k * ext, (size_t) stride * ext,
-                                  (const char *) inbuf + k * ext, (size_t) blocklen * ext,
-                                  (uint64_t) count, it, ext, (hipStream_t) stream);
-        } else {                            // block by block
-            for (MPIX_Aint b = 0; b < count && rc == MPIX_REDOP_SUCCESS; ++b)
-                rc = replace_rows((char *) inoutbuf + b * stride * ext, ext,
-                                  (const char *) inbuf + b * blocklen * ext, ext,
-                                  (uint64_t) blocklen, it, ext, (hipStream_t) stream);
-        }
-        return set_err(rc);
-    }
+    if (opi == kOpReplace)
+        return set_err(copy_blocks(inoutbuf, (uint64_t) stride, inbuf, (uint64_t) blocklen,
+                                   (uint64_t) count, (uint64_t) blocklen, it, ext,
+                                   (hipStream_t) stream));
     const Entry *e = gpu_entry(opi, it);
     if (!e)
         return set_err(MPIX_REDOP_ERR_TYPE);
@@ -2240,35 +2334,21 @@ int MPIX_Reduce_local_vector_async(const void *inbuf, void *inoutbuf, MPIX_Aint 
                                      (hipStream_t) stream)));
 }
 
+// the target is classified before anything is validated: the whole
+// stream-ordered call runs on the library stream
 int MPIX_Reduce_local_vector(const void *inbuf, void *inoutbuf, MPIX_Aint count,
                              MPIX_Aint blocklen, MPIX_Aint stride, MPIX_Datatype basic_type,
                              MPIX_Op op)
 {
-    int dev = 0;
-    const void *dp;
-    if (classify(inoutbuf, &dev, &dp) != Where::Device)
-        return set_err(MPIX_REDOP_ERR_BUFFER);
-    DeviceGuard guard(dev);
-    DevState *d = dev_state(dev);
-    if (!d)
-        return set_err(MPIX_REDOP_ERR_OTHER);
-    int rc = MPIX_Reduce_local_vector_async(inbuf, inoutbuf, count, blocklen, stride, basic_type,
-                                            op, d->s[0]);
-    int rc2 = wait_stream(d, d->s[0]);
-    return set_err(rc ? rc : rc2);
+    return set_err(on_library_stream(inoutbuf, [&](hipStream_t s) {
+        return MPIX_Reduce_local_vector_async(inbuf, inoutbuf, count, blocklen, stride,
+                                              basic_type, op, s);
+    }));
 }
 
 // ------------------------------------------------ fused get-accumulate
 // One implementation for both forms: the contiguous one is the vector target
 // with blocklen = stride = 1.
-static bool ranges_overlap(const void *a, uint64_t na, const void *b, uint64_t nb)
-{
-    const uintptr_t x = (uintptr_t) a, y = (uintptr_t) b;
-    return x < y + nb && y < x + na;
-}
-
-static bool no_buffer(const void *p) { return !p || p == (const void *) -1; }
-
 // Every check that needs no device: on success *n holds the packed element
 // count (0: nothing to do, no pointer was looked at).
 static int getacc_validate(const void *origin, const void *result, const void *target,
@@ -2280,7 +2360,7 @@ static int getacc_validate(const void *origin, const void *result, const void *t
         return MPIX_REDOP_ERR_COUNT;
     if (stride < blocklen)
         return MPIX_REDOP_ERR_ARG;      // overlapping target runs
-    if (is_builtin_op(op) && (op & 0xf) == 15)
+    if (is_builtin_op(op) && (op & 0xf) == kOpEqual)
         return MPIX_REDOP_ERR_OP;       // MPIX_EQUAL is no accumulate op
     int rc = validate(nullptr, nullptr, 0, dt, op, it, ext);
     if (rc != MPIX_REDOP_SUCCESS || count == 0 || blocklen == 0)
@@ -2291,140 +2371,88 @@ static int getacc_validate(const void *origin, const void *result, const void *t
     if (bl > cap || c > cap / bl || (c > 1 && st > (cap - bl) / (c - 1)))
         return MPIX_REDOP_ERR_COUNT;
     const uint32_t opi = op & 0xf;
-    const bool reads_origin = opi != 14;    // MPI_NO_OP: origin may be NULL
-    if (no_buffer(result) || no_buffer(target) || (reads_origin && no_buffer(origin)))
+    const bool reads_origin = opi != kOpNoOp;
+    if (missing_operand(origin, result, target, true, reads_origin))
         return MPIX_REDOP_ERR_BUFFER;
-    const uint64_t packed = c * bl * *ext, span = ((c - 1) * st + bl) * *ext;
-    if (ranges_overlap(result, packed, target, span) ||
-        (reads_origin && (ranges_overlap(origin, packed, target, span) ||
-                          ranges_overlap(origin, packed, result, packed))))
+    if (operands_overlap(origin, result, target, c * bl * *ext, ((c - 1) * st + bl) * *ext, true,
+                         reads_origin))
         return MPIX_REDOP_ERR_BUFFER;
-    if (opi < 13 && !getacc_entry(opi, *it))
+    if (opi < kOpReplace && !getacc_entry(opi, *it))
         return MPIX_REDOP_ERR_TYPE;     // a legal pair without a kernel
     *n = c * bl;
     return MPIX_REDOP_SUCCESS;
 }
 
-// Type-map copy (MPIR_Localcopy) of `count` blocks of `bl` elements between
-// two buffers whose blocks start every dp / sp elements.
-static int copy_blocks(void *dst, uint64_t dp, const void *src, uint64_t sp, uint64_t count,
-                       uint64_t bl, uint32_t it, uint64_t ext, hipStream_t s)
+// Placed operands: the launch on `s`.  NO_OP and REPLACE are the stream-ordered
+// copies (fetch, then replace); every other op is one fused kernel.
+static int getacc_launch(const void *po, void *pr, void *pt, uint64_t count, uint64_t bl,
+                         uint64_t st, uint32_t it, uint64_t ext, uint32_t opi, bool zc,
+                         hipStream_t s)
 {
-    if (dp == bl && sp == bl)
-        return replace_rows(dst, ext, src, ext, count * bl, it, ext, s);
-    PairMap pm;
-    if (!padded_pair(it, &pm))
-        return hip_err(hipMemcpy2DAsync(dst, dp * ext, src, sp * ext, bl * ext, count,
-                                        hipMemcpyDeviceToDevice, s));
-    int rc = MPIX_REDOP_SUCCESS;
-    if (bl <= count) {      // column k of every block
-        for (uint64_t k = 0; k < bl && rc == MPIX_REDOP_SUCCESS; ++k)
-            rc = replace_rows((char *) dst + k * ext, dp * ext, (const char *) src + k * ext,
-                              sp * ext, count, it, ext, s);
-    } else {                // block by block
-        for (uint64_t b = 0; b < count && rc == MPIX_REDOP_SUCCESS; ++b)
-            rc = replace_rows((char *) dst + b * dp * ext, ext, (const char *) src + b * sp * ext,
-                              ext, bl, it, ext, s);
-    }
-    return rc;
-}
-
-// Validated arguments: operand placement, then the launch on `s`.  NO_OP and
-// REPLACE are the stream-ordered copies (fetch, then replace); every other op
-// is one fused kernel.
-static int getacc_enqueue(const void *origin, void *result, void *target, uint64_t count,
-                          uint64_t bl, uint64_t st, uint32_t it, uint64_t ext, uint32_t op,
-                          hipStream_t s)
-{
-    const uint32_t opi = op & 0xf;
-    const void *po = origin, *pr, *pt;
-    int launch = -2;
-    bool zc = false;
-    if (!reachable(result, s, &launch, &pr, &zc) || !reachable(target, s, &launch, &pt, &zc) ||
-        (opi != 14 && !reachable(origin, s, &launch, &po, &zc)))
-        return MPIX_REDOP_ERR_BUFFER;
-    if (opi == 13 || opi == 14) {
-        int rc = copy_blocks((void *) pr, bl, pt, st, count, bl, it, ext, s);
-        if (rc == MPIX_REDOP_SUCCESS && opi == 13)
-            rc = copy_blocks((void *) pt, st, po, bl, count, bl, it, ext, s);
+    if (opi == kOpReplace || opi == kOpNoOp) {
+        int rc = copy_blocks(pr, bl, pt, st, count, bl, it, ext, s);
+        if (rc == MPIX_REDOP_SUCCESS && opi == kOpReplace)
+            rc = copy_blocks(pt, st, po, bl, count, bl, it, ext, s);
         return rc;
     }
     const mpix::GetaccEntry *e = getacc_entry(opi, it);
     if (!e)
         return MPIX_REDOP_ERR_TYPE;
     if (bl == st)
-        return hip_err(e->contig(po, (void *) pr, (void *) pt, count * bl, params(),
-                                 launch_cfg(zc), s));
-    return hip_err(e->vector(po, (void *) pr, (void *) pt, count, bl, st, params(), launch_cfg(),
-                             s));
+        return hip_err(e->contig(po, pr, pt, count * bl, params(), launch_cfg(zc), s));
+    return hip_err(e->vector(po, pr, pt, count, bl, st, params(), launch_cfg(), s));
 }
 
-static int getacc_async(const void *origin, void *result, void *target, MPIX_Aint count,
-                        MPIX_Aint blocklen, MPIX_Aint stride, uint32_t dt, uint32_t op,
-                        hipStream_t s)
+// Either form (sync: on the library stream): validate once, then placement
+// and the launch.
+static int getacc(const void *origin, void *result, void *target, MPIX_Aint count,
+                  MPIX_Aint blocklen, MPIX_Aint stride, uint32_t dt, uint32_t op, bool sync,
+                  hipStream_t stream)
 {
     uint32_t it;
     uint64_t ext, n;
     int rc = getacc_validate(origin, result, target, count, blocklen, stride, dt, op, &it, &ext, &n);
     if (rc != MPIX_REDOP_SUCCESS || n == 0)
         return rc;
-    return getacc_enqueue(origin, result, target, (uint64_t) count, (uint64_t) blocklen,
-                          (uint64_t) stride, it, ext, op, s);
-}
-
-// the synchronous forms: a device-memory target, the calling thread's library
-// stream of that device, and a wait on it (no in-kernel completion word)
-static int getacc_sync(const void *origin, void *result, void *target, MPIX_Aint count,
-                       MPIX_Aint blocklen, MPIX_Aint stride, uint32_t dt, uint32_t op)
-{
-    uint32_t it;
-    uint64_t ext, n;
-    int rc = getacc_validate(origin, result, target, count, blocklen, stride, dt, op, &it, &ext, &n);
-    if (rc != MPIX_REDOP_SUCCESS || n == 0)
-        return rc;
-    int dev = 0;
-    const void *dp;
-    if (classify(target, &dev, &dp) != Where::Device)
-        return MPIX_REDOP_ERR_BUFFER;
-    DeviceGuard guard(dev);
-    DevState *d = dev_state(dev);
-    if (!d)
-        return MPIX_REDOP_ERR_OTHER;
-    rc = getacc_enqueue(origin, result, target, (uint64_t) count, (uint64_t) blocklen,
-                        (uint64_t) stride, it, ext, op, d->s[0]);
-    const int rc2 = wait_stream(d, d->s[0]);
-    return rc ? rc : rc2;
+    return on_stream(sync, stream, target, [&](hipStream_t s) {
+        const uint32_t opi = op & 0xf;
+        Placed p{origin, result, target};
+        if (!place_operands(&p, true, false, opi != kOpNoOp, s))
+            return MPIX_REDOP_ERR_BUFFER;
+        return getacc_launch(p.origin, (void *) p.result, (void *) p.target, (uint64_t) count,
+                             (uint64_t) blocklen, (uint64_t) stride, it, ext, opi, p.zc, s);
+    });
 }
 
 int MPIX_Get_accumulate_local_async(const void *origin, void *result, void *target,
                                     MPIX_Aint count, MPIX_Datatype datatype, MPIX_Op op,
                                     void *stream)
 {
-    return set_err(getacc_async(origin, result, target, count, 1, 1, (uint32_t) datatype,
-                                (uint32_t) op, (hipStream_t) stream));
+    return set_err(getacc(origin, result, target, count, 1, 1, (uint32_t) datatype, (uint32_t) op,
+                          false, (hipStream_t) stream));
 }
 
 int MPIX_Get_accumulate_local(const void *origin, void *result, void *target, MPIX_Aint count,
                               MPIX_Datatype datatype, MPIX_Op op)
 {
-    return set_err(getacc_sync(origin, result, target, count, 1, 1, (uint32_t) datatype,
-                               (uint32_t) op));
+    return set_err(getacc(origin, result, target, count, 1, 1, (uint32_t) datatype, (uint32_t) op,
+                          true, nullptr));
 }
 
 int MPIX_Get_accumulate_local_vector_async(const void *origin, void *result, void *target,
                                            MPIX_Aint count, MPIX_Aint blocklen, MPIX_Aint stride,
                                            MPIX_Datatype basic_type, MPIX_Op op, void *stream)
 {
-    return set_err(getacc_async(origin, result, target, count, blocklen, stride,
-                                (uint32_t) basic_type, (uint32_t) op, (hipStream_t) stream));
+    return set_err(getacc(origin, result, target, count, blocklen, stride, (uint32_t) basic_type,
+                          (uint32_t) op, false, (hipStream_t) stream));
 }
 
 int MPIX_Get_accumulate_local_vector(const void *origin, void *result, void *target,
                                      MPIX_Aint count, MPIX_Aint blocklen, MPIX_Aint stride,
                                      MPIX_Datatype basic_type, MPIX_Op op)
 {
-    return set_err(getacc_sync(origin, result, target, count, blocklen, stride,
-                               (uint32_t) basic_type, (uint32_t) op));
+    return set_err(getacc(origin, result, target, count, blocklen, stride, (uint32_t) basic_type,
+                          (uint32_t) op, true, nullptr));
 }
 
 // The element runs of the flattened-iov forms (seg_counts in elements).
@@ -2527,7 +2555,7 @@ static int getacc_runs(const void *origin, void *result, void *target,
     if (rc != MPIX_REDOP_SUCCESS)
         return rc;
     const uint32_t opi = op & 0xf;
-    if (opi == 15)
+    if (opi == kOpEqual)
         return MPIX_REDOP_ERR_OP;       // MPIX_EQUAL is no accumulate op
     // total elements and the target's bounding byte range [lo, hi): lowest run
     // start to highest run end, zero-length runs aside; `over` once a packed
@@ -2554,38 +2582,33 @@ static int getacc_runs(const void *origin, void *result, void *target,
     }
     if (!over && total == 0)
         return MPIX_REDOP_SUCCESS;
-    const bool reads_origin = opi != 14;    // MPI_NO_OP: origin may be NULL
-    if (no_buffer(result) || no_buffer(target) || (reads_origin && no_buffer(origin)))
+    const bool reads_origin = opi != kOpNoOp;
+    if (missing_operand(origin, result, target, true, reads_origin))
         return MPIX_REDOP_ERR_BUFFER;
     const int64_t e = (int64_t) ext;
     if (!residues_aligned(runs, e))
         return MPIX_REDOP_ERR_ARG;
     if (over || hi - lo >= span_cap || total * ext >= (uint64_t) span_cap)
         return MPIX_REDOP_ERR_COUNT;
-    const uint64_t packed = total * ext, span = (uint64_t) (hi - lo);
-    const char *tlo = (const char *) target + (int64_t) lo;
-    if (ranges_overlap(result, packed, tlo, span) ||
-        (reads_origin && (ranges_overlap(origin, packed, tlo, span) ||
-                          ranges_overlap(origin, packed, result, packed))))
+    if (operands_overlap(origin, result, (const char *) target + (int64_t) lo, total * ext,
+                         (uint64_t) (hi - lo), true, reads_origin))
         return MPIX_REDOP_ERR_BUFFER;
     const mpix::GetaccIovEntry *en = nullptr;
-    if (opi < 13 && !(en = getacc_iov_entry(opi, it)))
+    if (opi < kOpReplace && !(en = getacc_iov_entry(opi, it)))
         return MPIX_REDOP_ERR_TYPE;     // a legal pair without a kernel
-    const void *po = origin, *pr, *pt;
-    int launch = -2;
-    if (!reachable(result, s, &launch, &pr) || !reachable(target, s, &launch, &pt) ||
-        (reads_origin && !reachable(origin, s, &launch, &po)))
+    Placed p{origin, result, target};
+    if (!place_operands(&p, true, false, reads_origin, s))
         return MPIX_REDOP_ERR_BUFFER;
     PairMap pm{0, 0};
     (void) padded_pair(it, &pm);
     return launch_groups(runs, e, s, [&](const ResidueGroup &g) {
-        void *tg = (char *) pt + g.resid;
+        void *tg = (char *) p.target + g.resid;
         if (en)
-            return en->iov(po, (void *) pr, tg, g.seg_off, g.prefix, g.src_off, g.n, g.total,
-                           params(), launch_cfg(), s);
-        return mpix::launch_getacc_iov_copy(opi == 13, (uint32_t) ext, pm.value_bytes, pm.loc_off,
-                                            po, (void *) pr, tg, g.seg_off, g.prefix, g.src_off,
-                                            g.n, g.total, launch_cfg(), s);
+            return en->iov(p.origin, (void *) p.result, tg, g.seg_off, g.prefix, g.src_off, g.n,
+                           g.total, params(), launch_cfg(), s);
+        return mpix::launch_getacc_iov_copy(copy_mode(opi, true), (uint32_t) ext, pm.value_bytes,
+                                            pm.loc_off, p.origin, (void *) p.result, tg, g.seg_off,
+                                            g.prefix, g.src_off, g.n, g.total, launch_cfg(), s);
     });
 }
 
@@ -2862,24 +2885,21 @@ static int plan_validate(const void *origin, const void *result, const void *tar
     *n = 0;
     if (!p)
         return MPIX_REDOP_ERR_ARG;
-    if (!is_builtin_op(op) || (op & 0xf) == 15 || !internal_ok(op, p->it))
+    if (!is_builtin_op(op) || (op & 0xf) == kOpEqual || !internal_ok(op, p->it))
         return MPIX_REDOP_ERR_OP;
     if (p->total == 0)
         return MPIX_REDOP_SUCCESS;
     const uint32_t opi = op & 0xf;
-    const bool reads_origin = !(fetch && opi == 14);
-    if ((fetch && no_buffer(result)) || no_buffer(target) || (reads_origin && no_buffer(origin)))
+    const bool reads_origin = !(fetch && opi == kOpNoOp);
+    if (missing_operand(origin, result, target, fetch, reads_origin))
         return MPIX_REDOP_ERR_BUFFER;
-    const uint64_t packed = p->total * p->ext, span = (uint64_t) (p->hi - p->lo);
-    const char *tlo = (const char *) target + p->lo;
-    if ((fetch && ranges_overlap(result, packed, tlo, span)) ||
-        (reads_origin && (ranges_overlap(origin, packed, tlo, span) ||
-                          (fetch && ranges_overlap(origin, packed, result, packed)))))
+    if (operands_overlap(origin, result, (const char *) target + p->lo, p->total * p->ext,
+                         (uint64_t) (p->hi - p->lo), fetch, reads_origin))
         return MPIX_REDOP_ERR_BUFFER;
     // a plan of one run launches through gpu_entry / getacc_entry instead: every
     // family is built from the one (type, op) table (redop_tables.h), so one
     // lookup answers for all
-    if (opi < 13 && !plan_entry(opi, p->it))
+    if (opi < kOpReplace && !plan_entry(opi, p->it))
         return MPIX_REDOP_ERR_TYPE;     // a legal pair without a kernel
     *n = p->total;
     return MPIX_REDOP_SUCCESS;
@@ -2893,182 +2913,83 @@ static int plan_enqueue(const void *origin, void *result, void *target, MPIX_Iov
                         uint32_t op, bool fetch, hipStream_t s)
 {
     const uint32_t opi = op & 0xf;
-    const bool reads_origin = !(fetch && opi == 14);
-    const void *po = origin, *pr = result, *pt;
-    int launch = -2;
-    bool zc = false;
-    if ((fetch && !reachable(result, s, &launch, &pr, &zc)) ||
-        !reachable(target, s, &launch, &pt, &zc) ||
-        (reads_origin && !reachable(origin, s, &launch, &po, &zc)))
+    Placed q{origin, result, target};
+    if (!place_operands(&q, fetch, false, !(fetch && opi == kOpNoOp), s))
         return MPIX_REDOP_ERR_BUFFER;
-    if (!fetch && opi == 14)
-        return MPIX_REDOP_SUCCESS;      // the reduce form's MPI_NO_OP
+    const void *po = q.origin;
+    void *pr = (void *) q.result;
+    if (!fetch && opi == kOpNoOp)
+        return MPIX_REDOP_SUCCESS;
     if (p->nrun == 1) {
-        char *t1 = (char *) pt + p->one_off;
+        char *t1 = (char *) q.target + p->one_off;
         if (!fetch)
-            return enqueue(po, t1, p->total, p->it, p->ext, op, s, nullptr, nullptr, 0, nullptr, zc);
-        if (opi == 13 || opi == 14) {
-            int rc = copy_blocks((void *) pr, 1, t1, 1, p->total, 1, p->it, p->ext, s);
-            if (rc == MPIX_REDOP_SUCCESS && opi == 13)
-                rc = copy_blocks(t1, 1, po, 1, p->total, 1, p->it, p->ext, s);
-            return rc;
-        }
-        const mpix::GetaccEntry *e = getacc_entry(opi, p->it);
-        if (!e)
-            return MPIX_REDOP_ERR_TYPE;
-        return hip_err(e->contig(po, (void *) pr, t1, p->total, params(), launch_cfg(zc), s));
+            return enqueue(po, t1, p->total, p->it, p->ext, op, s, nullptr, nullptr, 0, nullptr,
+                           q.zc);
+        return getacc_launch(po, pr, t1, p->total, 1, 1, p->it, p->ext, opi, q.zc, s);
     }
-    const mpix::PlanEntry *en = opi < 13 ? plan_entry(opi, p->it) : nullptr;
-    if (opi < 13 && !en)
+    const mpix::PlanEntry *en = opi < kOpReplace ? plan_entry(opi, p->it) : nullptr;
+    if (opi < kOpReplace && !en)
         return MPIX_REDOP_ERR_TYPE;
-    if (launch == -2)
-        launch = stream_device(s);
     char *tab;
-    int rc = plan_tables(p, launch, &tab);
+    int rc = plan_tables(p, q.launch == -2 ? stream_device(s) : q.launch, &tab);
     if (rc != MPIX_REDOP_SUCCESS)
         return rc;
     PairMap pm{0, 0};
     (void) padded_pair(p->it, &pm);
     const int32_t *tiles = (const int32_t *) (tab + p->rt.tab.size() * sizeof(int64_t));
-    const int mode = !fetch ? 2 : (opi == 13 ? 1 : 0);
     for (size_t g = 0; g < p->rt.resid.size() && rc == MPIX_REDOP_SUCCESS; ++g) {
         const ResidueGroup gr(p->rt, g, (const int64_t *) tab);
         const int64_t *t = gr.seg_off;      // the group's whole table
         const int32_t *tl = tiles + p->tile_base[g];
-        void *tg = (char *) pt + gr.resid;
+        void *tg = (char *) q.target + gr.resid;
         if (!en)
-            rc = hip_err(mpix::launch_plan_copy(mode, (uint32_t) p->ext, pm.value_bytes, pm.loc_off,
-                                                po, (void *) pr, tg, t, tl, gr.n, gr.total,
-                                                launch_cfg(), s));
+            rc = hip_err(mpix::launch_plan_copy(copy_mode(opi, fetch), (uint32_t) p->ext,
+                                                pm.value_bytes, pm.loc_off, po, pr, tg, t, tl, gr.n,
+                                                gr.total, launch_cfg(), s));
         else if (fetch)
-            rc = hip_err(en->getacc(po, (void *) pr, tg, t, tl, gr.n, gr.total, params(),
-                                    launch_cfg(), s));
+            rc = hip_err(en->getacc(po, pr, tg, t, tl, gr.n, gr.total, params(), launch_cfg(), s));
         else
             rc = hip_err(en->reduce(po, tg, t, tl, gr.n, gr.total, params(), launch_cfg(), s));
     }
     return rc;
 }
 
-static int plan_async(const void *origin, void *result, void *target, MPIX_Iov_plan plan,
-                      uint32_t op, bool fetch, hipStream_t s)
+// Either form of the reduce (fetch = false, no result) and the fetch entry.
+static int plan_run(const void *origin, void *result, void *target, MPIX_Iov_plan plan,
+                    uint32_t op, bool fetch, bool sync, hipStream_t stream)
 {
     uint64_t n;
     int rc = plan_validate(origin, result, target, plan, op, fetch, &n);
     if (rc != MPIX_REDOP_SUCCESS || n == 0)
         return rc;
-    return plan_enqueue(origin, result, target, plan, op, fetch, s);
-}
-
-// the synchronous forms, as getacc_sync: a device-memory target, the calling
-// thread's library stream of that device, and a wait on it
-static int plan_sync(const void *origin, void *result, void *target, MPIX_Iov_plan plan,
-                     uint32_t op, bool fetch)
-{
-    uint64_t n;
-    int rc = plan_validate(origin, result, target, plan, op, fetch, &n);
-    if (rc != MPIX_REDOP_SUCCESS || n == 0)
-        return rc;
-    int dev = 0;
-    const void *dp;
-    if (classify(target, &dev, &dp) != Where::Device)
-        return MPIX_REDOP_ERR_BUFFER;
-    DeviceGuard guard(dev);
-    DevState *d = dev_state(dev);
-    if (!d)
-        return MPIX_REDOP_ERR_OTHER;
-    rc = plan_enqueue(origin, result, target, plan, op, fetch, d->s[0]);
-    const int rc2 = wait_stream(d, d->s[0]);
-    return rc ? rc : rc2;
+    return on_stream(sync, stream, target, [&](hipStream_t s) {
+        return plan_enqueue(origin, result, target, plan, op, fetch, s);
+    });
 }
 
 int MPIX_Reduce_local_plan_async(const void *inbuf, void *inoutbuf, MPIX_Iov_plan plan, MPIX_Op op,
                                  void *stream)
 {
-    return set_err(plan_async(inbuf, nullptr, inoutbuf, plan, (uint32_t) op, false,
-                              (hipStream_t) stream));
+    return set_err(plan_run(inbuf, nullptr, inoutbuf, plan, (uint32_t) op, false, false,
+                            (hipStream_t) stream));
 }
 
 int MPIX_Reduce_local_plan(const void *inbuf, void *inoutbuf, MPIX_Iov_plan plan, MPIX_Op op)
 {
-    return set_err(plan_sync(inbuf, nullptr, inoutbuf, plan, (uint32_t) op, false));
+    return set_err(plan_run(inbuf, nullptr, inoutbuf, plan, (uint32_t) op, false, true, nullptr));
 }
 
 int MPIX_Get_accumulate_local_plan_async(const void *origin, void *result, void *target,
                                          MPIX_Iov_plan plan, MPIX_Op op, void *stream)
 {
-    return set_err(plan_async(origin, result, target, plan, (uint32_t) op, true,
-                              (hipStream_t) stream));
+    return set_err(plan_run(origin, result, target, plan, (uint32_t) op, true, false,
+                            (hipStream_t) stream));
 }
 
 int MPIX_Get_accumulate_local_plan(const void *origin, void *result, void *target,
                                    MPIX_Iov_plan plan, MPIX_Op op)
 {
-    return set_err(plan_sync(origin, result, target, plan, (uint32_t) op, true));
-}
-
-// MPI_Compare_and_swap's local step.  MPIR_Type_is_rma_atomic
-// (rmatypeutil.c:18-30): the integer group of internal types only.
-static int cas_validate(const void *origin, const void *compare, const void *result,
-                        const void *target, uint32_t dt, uint32_t *size)
-{
-    const uint32_t it = to_internal(dt);
-    if (it == kNull || !is_builtin(it) || !(it & 0x800000u) || (it & 0x400000u))
-        return MPIX_REDOP_ERR_TYPE;
-    const uint32_t kind = it & 0x0f0000u;
-    const uint64_t ext = extent_of(it);
-    if ((kind != 0x010000u && kind != 0x020000u) ||
-        (ext != 1 && ext != 2 && ext != 4 && ext != 8 && ext != 16))
-        return MPIX_REDOP_ERR_TYPE;
-    if (no_buffer(origin) || no_buffer(compare) || no_buffer(result) || no_buffer(target))
-        return MPIX_REDOP_ERR_BUFFER;
-    // origin and compare are both only read: they may share an address
-    if (ranges_overlap(result, ext, origin, ext) || ranges_overlap(result, ext, compare, ext) ||
-        ranges_overlap(result, ext, target, ext) || ranges_overlap(target, ext, origin, ext) ||
-        ranges_overlap(target, ext, compare, ext))
-        return MPIX_REDOP_ERR_BUFFER;
-    *size = (uint32_t) ext;
-    return MPIX_REDOP_SUCCESS;
-}
-
-static int cas_enqueue(const void *origin, const void *compare, void *result, void *target,
-                       uint32_t size, hipStream_t s)
-{
-    const void *po, *pc, *pr, *pt;
-    int launch = -2;
-    if (!reachable(origin, s, &launch, &po) || !reachable(compare, s, &launch, &pc) ||
-        !reachable(result, s, &launch, &pr) || !reachable(target, s, &launch, &pt))
-        return MPIX_REDOP_ERR_BUFFER;
-    return hip_err(mpix::launch_cas(size, po, pc, (void *) pr, (void *) pt, s));
-}
-
-int MPIX_Compare_and_swap_local_async(const void *origin, const void *compare, void *result,
-                                      void *target, MPIX_Datatype datatype, void *stream)
-{
-    uint32_t size;
-    int rc = cas_validate(origin, compare, result, target, (uint32_t) datatype, &size);
-    if (rc != MPIX_REDOP_SUCCESS)
-        return set_err(rc);
-    return set_err(cas_enqueue(origin, compare, result, target, size, (hipStream_t) stream));
-}
-
-int MPIX_Compare_and_swap_local(const void *origin, const void *compare, void *result,
-                                void *target, MPIX_Datatype datatype)
-{
-    uint32_t size;
-    int rc = cas_validate(origin, compare, result, target, (uint32_t) datatype, &size);
-    if (rc != MPIX_REDOP_SUCCESS)
-        return set_err(rc);
-    int dev = 0;
-    const void *dp;
-    if (classify(target, &dev, &dp) != Where::Device)
-        return set_err(MPIX_REDOP_ERR_BUFFER);
-    DeviceGuard guard(dev);
-    DevState *d = dev_state(dev);
-    if (!d)
-        return set_err(MPIX_REDOP_ERR_OTHER);
-    rc = cas_enqueue(origin, compare, result, target, size, d->s[0]);
-    const int rc2 = wait_stream(d, d->s[0]);
-    return set_err(rc ? rc : rc2);
+    return set_err(plan_run(origin, result, target, plan, (uint32_t) op, true, true, nullptr));
 }
 
 // ------------------------------------- element-atomic accumulate
@@ -3084,13 +3005,13 @@ static const mpix::AtomicEntry *atomic_entry(uint32_t opi, uint32_t it)
 
 static bool atomic_extent(uint64_t ext) { return ext == 1 || ext == 2 || ext == 4 || ext == 8; }
 
-// MPIR_Type_is_rma_atomic (rmatypeutil.c:18-30), cas_validate's rule
+// MPIR_Type_is_rma_atomic (rmatypeutil.c:18-30): the integer group of
+// internal types only
 static bool rma_atomic_type(uint32_t it)
 {
     if (it == kNull || !is_builtin(it) || !(it & 0x800000u) || (it & 0x400000u))
         return false;
-    const uint32_t kind = it & 0x0f0000u;
-    return kind == 0x010000u || kind == 0x020000u;
+    return integer_kind(it & 0x0f0000u);
 }
 
 // The pair alone, no HIP call: legal, a kernel in the table, and an extent
@@ -3099,12 +3020,12 @@ static int atomic_supported(uint32_t op, uint32_t it)
 {
     if (it == kNull || !atomic_extent(extent_of(it)))
         return 0;
-    if (op == 0x18000000u)
+    if (op == kOpNull)
         return rma_atomic_type(it) ? 1 : 0;
-    if (!is_builtin_op(op) || (op & 0xf) == 15 || !internal_ok(op, it))
+    if (!is_builtin_op(op) || (op & 0xf) == kOpEqual || !internal_ok(op, it))
         return 0;
     const uint32_t opi = op & 0xf;
-    if (opi == 13 || opi == 14)
+    if (opi == kOpReplace || opi == kOpNoOp)
         return 1;
     const mpix::AtomicEntry *e = atomic_entry(opi, it);
     return (e && e->acc && e->getacc) ? 1 : 0;
@@ -3121,7 +3042,7 @@ static int atomic_validate(const void *origin, const void *result, const void *t
     *n = 0;
     if (count < 0)
         return MPIX_REDOP_ERR_COUNT;
-    if (is_builtin_op(op) && (op & 0xf) == 15)
+    if (is_builtin_op(op) && (op & 0xf) == kOpEqual)
         return MPIX_REDOP_ERR_OP;       // MPIX_EQUAL is no accumulate op
     int rc = validate(nullptr, nullptr, 0, dt, op, it, ext);
     if (rc != MPIX_REDOP_SUCCESS || count == 0)
@@ -3129,13 +3050,10 @@ static int atomic_validate(const void *origin, const void *result, const void *t
     const uint64_t c = (uint64_t) count;
     if (c > ((uint64_t) 1 << 56) / *ext)
         return MPIX_REDOP_ERR_COUNT;
-    const bool reads_origin = (op & 0xf) != 14;     // MPI_NO_OP: origin may be NULL
-    if ((fetch && no_buffer(result)) || no_buffer(target) || (reads_origin && no_buffer(origin)))
+    const bool reads_origin = (op & 0xf) != kOpNoOp;    // with or without a result
+    if (missing_operand(origin, result, target, fetch, reads_origin))
         return MPIX_REDOP_ERR_BUFFER;
-    const uint64_t bytes = c * *ext;
-    if ((fetch && ranges_overlap(result, bytes, target, bytes)) ||
-        (reads_origin && (ranges_overlap(origin, bytes, target, bytes) ||
-                          (fetch && ranges_overlap(origin, bytes, result, bytes)))))
+    if (operands_overlap(origin, result, target, c * *ext, c * *ext, fetch, reads_origin))
         return MPIX_REDOP_ERR_BUFFER;
     if (!atomic_supported(op, *it))
         return MPIX_REDOP_ERR_TYPE;     // no kernel, or no atomic of this extent
@@ -3161,72 +3079,37 @@ static int atomic_enqueue(const void *origin, void *result, void *target, uint64
                           uint32_t it, uint64_t ext, uint32_t op, bool fetch, hipStream_t s)
 {
     const uint32_t opi = op & 0xf;
-    int launch = stream_device(s);
-    if (!atomic_target_ok(target, launch))
+    Placed p{origin, result, target, stream_device(s)};
+    if (!atomic_target_ok(target, p.launch) || !place_operands(&p, fetch, true, opi != kOpNoOp, s))
         return MPIX_REDOP_ERR_BUFFER;
-    const void *po = origin, *pr = result;
-    bool zc = false;
-    if ((fetch && !reachable(result, s, &launch, &pr, &zc)) ||
-        (opi != 14 && !reachable(origin, s, &launch, &po, &zc)))
-        return MPIX_REDOP_ERR_BUFFER;
-    if (opi == 14 && !fetch)
+    if (opi == kOpNoOp && !fetch)
         return MPIX_REDOP_SUCCESS;
-    const LaunchCfg cfg = launch_cfg(zc);
-    if (opi == 13 || opi == 14) {
+    const LaunchCfg cfg = launch_cfg(p.zc);
+    if (opi == kOpReplace || opi == kOpNoOp) {
         PairMap pm{0, 0};
         (void) padded_pair(it, &pm);
-        return hip_err(mpix::launch_atomic_copy(opi == 14 ? 0 : fetch ? 1 : 2, (uint32_t) ext,
-                                                pm.value_bytes, pm.loc_off, po, (void *) pr, target,
-                                                count, cfg, s));
+        return hip_err(mpix::launch_atomic_copy(copy_mode(opi, fetch), (uint32_t) ext,
+                                                pm.value_bytes, pm.loc_off, p.origin,
+                                                (void *) p.result, target, count, cfg, s));
     }
     const mpix::AtomicEntry *e = atomic_entry(opi, it);
     if (!e || !e->acc || !e->getacc)
         return MPIX_REDOP_ERR_TYPE;
     if (fetch)
-        return hip_err(e->getacc(po, (void *) pr, target, count, params(), cfg, s));
-    return hip_err(e->acc(po, target, count, params(), cfg, s));
+        return hip_err(e->getacc(p.origin, (void *) p.result, target, count, params(), cfg, s));
+    return hip_err(e->acc(p.origin, target, count, params(), cfg, s));
 }
 
-static int atomic_async(const void *origin, void *result, void *target, MPIX_Aint count,
-                        uint32_t dt, uint32_t op, bool fetch, hipStream_t s)
+// Either form of the accumulate (fetch = false, no result) and the fetch entry.
+static int atomic_run(const void *origin, void *result, void *target, MPIX_Aint count, uint32_t dt,
+                      uint32_t op, bool fetch, bool sync, hipStream_t stream)
 {
     uint32_t it;
     uint64_t ext, n;
     int rc = atomic_validate(origin, result, target, count, dt, op, fetch, &it, &ext, &n);
     if (rc != MPIX_REDOP_SUCCESS || n == 0)
         return rc;
-    return atomic_enqueue(origin, result, target, n, it, ext, op, fetch, s);
-}
-
-// the synchronous forms: the calling thread's library stream of the target's
-// device, and a wait on it
-extern "C++" {
-template <class F>
-static int atomic_on_library_stream(const void *target, F enqueue)
-{
-    int dev = 0;
-    const void *dp;
-    if (classify(target, &dev, &dp) != Where::Device)
-        return MPIX_REDOP_ERR_BUFFER;
-    DeviceGuard guard(dev);
-    DevState *d = dev_state(dev);
-    if (!d)
-        return MPIX_REDOP_ERR_OTHER;
-    const int rc = enqueue(d->s[0]);
-    const int rc2 = wait_stream(d, d->s[0]);
-    return rc ? rc : rc2;
-}
-}   // extern "C++"
-
-static int atomic_sync(const void *origin, void *result, void *target, MPIX_Aint count,
-                       uint32_t dt, uint32_t op, bool fetch)
-{
-    uint32_t it;
-    uint64_t ext, n;
-    int rc = atomic_validate(origin, result, target, count, dt, op, fetch, &it, &ext, &n);
-    if (rc != MPIX_REDOP_SUCCESS || n == 0)
-        return rc;
-    return atomic_on_library_stream(target, [&](hipStream_t s) {
+    return on_stream(sync, stream, target, [&](hipStream_t s) {
         return atomic_enqueue(origin, result, target, n, it, ext, op, fetch, s);
     });
 }
@@ -3234,81 +3117,113 @@ static int atomic_sync(const void *origin, void *result, void *target, MPIX_Aint
 int MPIX_Accumulate_local_atomic_async(const void *origin, void *target, MPIX_Aint count,
                                        MPIX_Datatype datatype, MPIX_Op op, void *stream)
 {
-    return set_err(atomic_async(origin, nullptr, target, count, (uint32_t) datatype, (uint32_t) op,
-                                false, (hipStream_t) stream));
+    return set_err(atomic_run(origin, nullptr, target, count, (uint32_t) datatype, (uint32_t) op,
+                              false, false, (hipStream_t) stream));
 }
 
 int MPIX_Accumulate_local_atomic(const void *origin, void *target, MPIX_Aint count,
                                  MPIX_Datatype datatype, MPIX_Op op)
 {
-    return set_err(atomic_sync(origin, nullptr, target, count, (uint32_t) datatype, (uint32_t) op,
-                               false));
+    return set_err(atomic_run(origin, nullptr, target, count, (uint32_t) datatype, (uint32_t) op,
+                              false, true, nullptr));
 }
 
 int MPIX_Get_accumulate_local_atomic_async(const void *origin, void *result, void *target,
                                            MPIX_Aint count, MPIX_Datatype datatype, MPIX_Op op,
                                            void *stream)
 {
-    return set_err(atomic_async(origin, result, target, count, (uint32_t) datatype, (uint32_t) op,
-                                true, (hipStream_t) stream));
+    return set_err(atomic_run(origin, result, target, count, (uint32_t) datatype, (uint32_t) op,
+                              true, false, (hipStream_t) stream));
 }
 
 int MPIX_Get_accumulate_local_atomic(const void *origin, void *result, void *target,
                                      MPIX_Aint count, MPIX_Datatype datatype, MPIX_Op op)
 {
-    return set_err(atomic_sync(origin, result, target, count, (uint32_t) datatype, (uint32_t) op,
-                               true));
+    return set_err(atomic_run(origin, result, target, count, (uint32_t) datatype, (uint32_t) op,
+                              true, true, nullptr));
 }
 
-// cas_validate's checks, then this family's: no 16-byte atomic (MPI_ERR_TYPE),
-// a target aligned to its size (MPI_ERR_BUFFER)
-static int cas_atomic_validate(const void *origin, const void *compare, const void *result,
-                               const void *target, uint32_t dt, uint32_t *size)
+// ------------------------------------- compare-and-swap
+// MPI_Compare_and_swap's local step on one element of an RMA-atomic type, as
+// a one-thread kernel or (atomic) as one device-scope compare-exchange.  The
+// atomic form's two checks come last: no 16-byte atomic (MPI_ERR_TYPE), a
+// target aligned to its size (MPI_ERR_BUFFER).
+static int cas_validate(const void *origin, const void *compare, const void *result,
+                        const void *target, uint32_t dt, bool atomic, uint32_t *size)
 {
-    int rc = cas_validate(origin, compare, result, target, dt, size);
-    if (rc != MPIX_REDOP_SUCCESS)
-        return rc;
-    if (!atomic_extent(*size))
+    const uint32_t it = to_internal(dt);
+    const uint64_t ext = extent_of(it);
+    if (!rma_atomic_type(it) || (!atomic_extent(ext) && ext != 16))
         return MPIX_REDOP_ERR_TYPE;
-    if ((uintptr_t) target % *size)
+    if (no_buffer(origin) || no_buffer(compare) || no_buffer(result) || no_buffer(target))
         return MPIX_REDOP_ERR_BUFFER;
+    // origin and compare are both only read: they may share an address
+    if (ranges_overlap(result, ext, origin, ext) || ranges_overlap(result, ext, compare, ext) ||
+        ranges_overlap(result, ext, target, ext) || ranges_overlap(target, ext, origin, ext) ||
+        ranges_overlap(target, ext, compare, ext))
+        return MPIX_REDOP_ERR_BUFFER;
+    if (atomic && !atomic_extent(ext))
+        return MPIX_REDOP_ERR_TYPE;
+    if (atomic && (uintptr_t) target % ext)
+        return MPIX_REDOP_ERR_BUFFER;
+    *size = (uint32_t) ext;
     return MPIX_REDOP_SUCCESS;
 }
 
-static int cas_atomic_enqueue(const void *origin, const void *compare, void *result, void *target,
-                              uint32_t size, hipStream_t s)
+// Placement -- the atomic form's target by atomic_target_ok, first; otherwise
+// origin, compare, result, target -- and the launch.
+static int cas_enqueue(const void *origin, const void *compare, void *result, void *target,
+                       uint32_t size, bool atomic, hipStream_t s)
 {
-    int launch = stream_device(s);
-    if (!atomic_target_ok(target, launch))
+    const void *po, *pc, *pr, *pt = target;
+    int launch = -2;
+    if (atomic && !atomic_target_ok(target, launch = stream_device(s)))
         return MPIX_REDOP_ERR_BUFFER;
-    const void *po, *pc, *pr;
     if (!reachable(origin, s, &launch, &po) || !reachable(compare, s, &launch, &pc) ||
-        !reachable(result, s, &launch, &pr))
+        !reachable(result, s, &launch, &pr) || (!atomic && !reachable(target, s, &launch, &pt)))
         return MPIX_REDOP_ERR_BUFFER;
-    return hip_err(mpix::launch_cas_atomic(size, po, pc, (void *) pr, target, s));
+    return hip_err((atomic ? mpix::launch_cas_atomic : mpix::launch_cas)(size, po, pc, (void *) pr,
+                                                                         (void *) pt, s));
+}
+
+static int cas_run(const void *origin, const void *compare, void *result, void *target,
+                   uint32_t dt, bool atomic, bool sync, hipStream_t stream)
+{
+    uint32_t size;
+    int rc = cas_validate(origin, compare, result, target, dt, atomic, &size);
+    if (rc != MPIX_REDOP_SUCCESS)
+        return rc;
+    return on_stream(sync, stream, target, [&](hipStream_t s) {
+        return cas_enqueue(origin, compare, result, target, size, atomic, s);
+    });
+}
+
+int MPIX_Compare_and_swap_local_async(const void *origin, const void *compare, void *result,
+                                      void *target, MPIX_Datatype datatype, void *stream)
+{
+    return set_err(cas_run(origin, compare, result, target, (uint32_t) datatype, false, false,
+                           (hipStream_t) stream));
+}
+
+int MPIX_Compare_and_swap_local(const void *origin, const void *compare, void *result,
+                                void *target, MPIX_Datatype datatype)
+{
+    return set_err(cas_run(origin, compare, result, target, (uint32_t) datatype, false, true,
+                           nullptr));
 }
 
 int MPIX_Compare_and_swap_local_atomic_async(const void *origin, const void *compare, void *result,
                                              void *target, MPIX_Datatype datatype, void *stream)
 {
-    uint32_t size;
-    int rc = cas_atomic_validate(origin, compare, result, target, (uint32_t) datatype, &size);
-    if (rc != MPIX_REDOP_SUCCESS)
-        return set_err(rc);
-    return set_err(cas_atomic_enqueue(origin, compare, result, target, size,
-                                      (hipStream_t) stream));
+    return set_err(cas_run(origin, compare, result, target, (uint32_t) datatype, true, false,
+                           (hipStream_t) stream));
 }
 
 int MPIX_Compare_and_swap_local_atomic(const void *origin, const void *compare, void *result,
                                        void *target, MPIX_Datatype datatype)
 {
-    uint32_t size;
-    int rc = cas_atomic_validate(origin, compare, result, target, (uint32_t) datatype, &size);
-    if (rc != MPIX_REDOP_SUCCESS)
-        return set_err(rc);
-    return set_err(atomic_on_library_stream(target, [&](hipStream_t s) {
-        return cas_atomic_enqueue(origin, compare, result, target, size, s);
-    }));
+    return set_err(cas_run(origin, compare, result, target, (uint32_t) datatype, true, true,
+                           nullptr));
 }
 
 int MPIX_Accumulate_atomic_is_supported(MPIX_Op op, MPIX_Datatype datatype)
@@ -3343,9 +3258,9 @@ int MPIX_Reduce_local_multi_async(const void *const *inbufs, int ninputs, void *
     inbufs = dins;
     inoutbuf = (void *) pio;
     uint32_t opi = (uint32_t) op & 0xf;
-    if (opi == 14)
+    if (opi == kOpNoOp)
         return set_err(MPIX_REDOP_SUCCESS);
-    if (opi == 13)      // REPLACE k times = copy of the last input
+    if (opi == kOpReplace)      // REPLACE k times = copy of the last input
         return set_err(replace_rows(inoutbuf, ext, inbufs[ninputs - 1], ext, (uint64_t) count, it,
                                     ext, (hipStream_t) stream));
     const Entry *e = gpu_entry(opi, it);
@@ -3376,7 +3291,7 @@ int MPIX_Reduce_local_tree_async(const void *const *inbufs, int ninputs, void *o
             (uint64_t) count > ((uint64_t) 1 << 56) / ext)
             rc = MPIX_REDOP_ERR_COUNT;
         if (rc == MPIX_REDOP_SUCCESS && same && count > 0 &&
-            (!outbuf || outbuf == (void *) -1))
+            no_buffer(outbuf))
             rc = MPIX_REDOP_ERR_BUFFER;
         if (rc != MPIX_REDOP_SUCCESS)
             return set_err(rc);
@@ -3384,7 +3299,7 @@ int MPIX_Reduce_local_tree_async(const void *const *inbufs, int ninputs, void *o
     if (count == 0)
         return set_err(MPIX_REDOP_SUCCESS);
     uint32_t opi = (uint32_t) op & 0xf;
-    if (opi == 15)
+    if (opi == kOpEqual)
         return set_err(MPIX_REDOP_ERR_OP);      // EQUAL is never split or folded
     const void *dins[mpix::kMaxMultiInputs];
     const void *pout;
@@ -3399,8 +3314,8 @@ int MPIX_Reduce_local_tree_async(const void *const *inbufs, int ninputs, void *o
         if (inbufs[q])
             last = q;
     }
-    if (opi == 13 || opi == 14) {   // REPLACE folds to the last present slot, NO_OP to the first
-        const void *src = dins[opi == 13 ? last : 0];
+    if (opi == kOpReplace || opi == kOpNoOp) {  // fold to the last present slot / to the first
+        const void *src = dins[opi == kOpReplace ? last : 0];
         if (src == pout)
             return set_err(MPIX_REDOP_SUCCESS);
         return set_err(replace_rows((void *) pout, ext, src, ext, (uint64_t) count, it, ext,
@@ -3486,9 +3401,9 @@ static int has_gpu_path(uint32_t op, uint32_t it)
     if (it == kNull || extent_of(it) == 0 || !internal_ok(op, it))
         return 0;
     uint32_t opi = op & 0xf;
-    if (opi == 13 || opi == 14)
+    if (opi == kOpReplace || opi == kOpNoOp)
         return 1;
-    if (opi == 15)
+    if (opi == kOpEqual)
         return (it & 0xffffff00u) == U8;
     return gpu_entry(opi, it) ? 1 : 0;
 }

@@ -134,13 +134,19 @@ const GetaccIovEntry *lookup_getacc_iov_int(int raw, int opi);
 const GetaccIovEntry *lookup_getacc_iov_fp(int raw, int opi);
 const GetaccIovEntry *lookup_getacc_iov_pair(int raw, int opi);
 
-// MPI_NO_OP (gather the runs into the packed result) and, `replace`,
-// MPI_REPLACE (then scatter the packed origin's type map over the runs) on the
-// same table, one launch: elements of `extent` bytes whose type map is the
-// whole extent (value_bytes == 0) or a value of value_bytes at 0 and an int at
-// loc_off (the padded pairs).  hipErrorInvalidValue for a layout without a
-// kernel.  inst_getacc_copy.hip.
-hipError_t launch_getacc_iov_copy(bool replace, uint32_t extent, uint32_t value_bytes,
+// What the copy launchers of MPI_NO_OP / MPI_REPLACE do with the target's
+// elements: load them into the packed result (the fetch forms' MPI_NO_OP), also
+// put the packed origin in their place (their MPI_REPLACE), or only that (the
+// forms without a result).
+enum CopyMode { kCopyFetch = 0, kCopySwap = 1, kCopyStore = 2 };
+
+// kCopyFetch (gather the runs into the packed result) and kCopySwap (then
+// scatter the packed origin's type map over the runs) on the same table, one
+// launch: elements of `extent` bytes whose type map is the whole extent
+// (value_bytes == 0) or a value of value_bytes at 0 and an int at loc_off (the
+// padded pairs).  hipErrorInvalidValue for a layout without a kernel.
+// inst_getacc_copy.hip.
+hipError_t launch_getacc_iov_copy(CopyMode mode, uint32_t extent, uint32_t value_bytes,
                                   uint32_t loc_off, const void *origin, void *result, void *target,
                                   const int64_t *d_seg_off, const int64_t *d_prefix,
                                   const int64_t *d_src_off, int64_t nseg, uint64_t total,
@@ -163,11 +169,11 @@ const PlanEntry *lookup_plan_int(int raw, int opi);
 const PlanEntry *lookup_plan_fp(int raw, int opi);
 const PlanEntry *lookup_plan_pair(int raw, int opi);
 
-// The type-map copies over the same tables: mode 0 gathers the runs into the
-// packed result (the fetch form's MPI_NO_OP), 1 also scatters the packed origin
-// over them (its MPI_REPLACE), 2 scatters only (the reduce form's MPI_REPLACE,
-// result unused).  Layouts as launch_getacc_iov_copy.  inst_plan_copy.hip.
-hipError_t launch_plan_copy(int mode, uint32_t extent, uint32_t value_bytes, uint32_t loc_off,
+// The type-map copies over the same tables: kCopyFetch gathers the runs into
+// the packed result, kCopySwap also scatters the packed origin over them,
+// kCopyStore scatters only (the reduce form's MPI_REPLACE, result unused).
+// Layouts as launch_getacc_iov_copy.  inst_plan_copy.hip.
+hipError_t launch_plan_copy(CopyMode mode, uint32_t extent, uint32_t value_bytes, uint32_t loc_off,
                             const void *origin, void *result, void *target, const int64_t *d_tab,
                             const int32_t *d_tile, int64_t nseg, uint64_t total,
                             const LaunchCfg &, hipStream_t);
@@ -196,11 +202,11 @@ const AtomicEntry *lookup_acc_atomic_pair(int raw, int opi);
 
 // MPI_NO_OP and MPI_REPLACE of the atomic entries on elements of `extent`
 // bytes (1, 2, 4, 8) whose type map is the whole extent (value_bytes == 0) or
-// a value and an int (the padded 8-byte pair): mode 0 an atomic load per
-// element into the result, 1 an atomic exchange of the type map, 2 an atomic
-// store of it (no result).  hipErrorInvalidValue for a layout without a
-// kernel.  inst_acc_atomic_copy.hip.
-hipError_t launch_atomic_copy(int mode, uint32_t extent, uint32_t value_bytes, uint32_t loc_off,
+// a value and an int (the padded 8-byte pair): kCopyFetch an atomic load per
+// element into the result, kCopySwap an atomic exchange of the type map,
+// kCopyStore an atomic store of it (no result).  hipErrorInvalidValue for a
+// layout without a kernel.  inst_acc_atomic_copy.hip.
+hipError_t launch_atomic_copy(CopyMode mode, uint32_t extent, uint32_t value_bytes, uint32_t loc_off,
                               const void *origin, void *result, void *target, uint64_t count,
                               const LaunchCfg &, hipStream_t);
 

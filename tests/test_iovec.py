@@ -245,28 +245,33 @@ def test_iov_misaligned_offset_refused(R):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('dt', [DOUBLE_INT, LONG_INT, SHORT_INT, FLOAT_INT])
+@pytest.mark.parametrize('dt', [DOUBLE_INT, LONG_INT, SHORT_INT, FLOAT_INT, MPI_DOUBLE])
 def test_replace_keeps_padding_on_gpu(R, oracle, dt):
-    """MPI_REPLACE on every entry point: contiguous (sync), vector target,
-    multi-input, all against the oracle's typemap copy"""
+    """MPI_REPLACE on every entry point: contiguous (sync), vector target
+    (stride == blocklen, the contiguous shortcut, included), multi-input, all
+    against the oracle's typemap copy; MPI_DOUBLE stands for the types
+    without padding"""
     from mpich_amd import handles as H
     rng = np.random.default_rng(dt & 0xff)
     n = 10007
-    src, tgt = random_pairs(rng, dt, n), random_pairs(rng, dt, n)
+
+    def rand(k):
+        return random_pairs(rng, dt, k) if dt in PAIRS else rng.uniform(-1, 1, k)
+    src, tgt = rand(n), rand(n)
     dd = _dev(tgt)
     assert R.MPI_Reduce_local(_dev(src), dd, n, dt, H.MPI_REPLACE) == 0
     exp = tgt.view(np.uint8).copy()
     oracle.reduce_local(src.view(np.uint8).copy(), exp, n, dt, REPLACE)
     assert _host(dd).tobytes() == exp.tobytes()
-    for bl, st, cnt in ((1, 2, 3001), (3, 5, 2000), (700, 701, 3)):
-        s2 = random_pairs(rng, dt, cnt * bl)
-        t2 = random_pairs(rng, dt, cnt * st)
+    for bl, st, cnt in ((1, 2, 3001), (3, 5, 2000), (700, 701, 3), (1, 1, 3001), (3, 3, 2000)):
+        s2 = rand(cnt * bl)
+        t2 = rand(cnt * st)
         d2 = _dev(t2)
         assert R.reduce_local_vector(_dev(s2), d2, cnt, bl, st, dt, H.MPI_REPLACE, sync=True) == 0
         e2 = t2.view(np.uint8).copy()
         oracle.reduce_local_vector(s2.view(np.uint8).copy(), e2, cnt, bl, st, dt, REPLACE)
         assert _host(d2).tobytes() == e2.tobytes(), (bl, st)
-    ins = [random_pairs(rng, dt, n) for _ in range(3)]
+    ins = [rand(n) for _ in range(3)]
     d3 = _dev(tgt)
     assert R.reduce_local_multi_async([_dev(x) for x in ins], d3, n, dt, H.MPI_REPLACE) == 0
     e3 = tgt.view(np.uint8).copy()

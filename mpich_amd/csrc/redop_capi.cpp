@@ -13,25 +13,22 @@
 
 #include <ctype.h>
 #include <limits.h>
-#include <pthread.h>
 #include <sched.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <linux/futex.h>
-#include <sys/syscall.h>
 #include <unistd.h>
 
 #include <atomic>
 #include <chrono>
 #include <string>
 #include <mutex>
-#include <thread>
 #include <vector>
 
 #include "mpix_redop.h"
 #include "redop_dispatch.h"
+#include "redop_hostpath.h"
 
 using mpix::Entry;
 using mpix::LaunchCfg;
@@ -490,6 +487,34 @@ thread_local int t_last_error = 0;
 
 constexpr int kMaxDev = 64;
 constexpr int kSyncTimingMax = 1 << 16;    // calls one MPIX_Redop_sync_timing covers
+
+// Page-locked host memory and its device mapping: the bounce buffer, each
+// worker's slot and the wave's ring.
+struct PinnedBuf {
+    char *host = nullptr, *dev = nullptr;
+    size_t bytes = 0;
+    bool alloc(size_t n)
+    {
+        void *h = nullptr, *hd = nullptr;
+        if (hipHostMalloc(&h, n, hipHostMallocDefault) != hipSuccess)
+            return false;
+        if (hipHostGetDevicePointer(&hd, h, 0) != hipSuccess) {
+            (void) hipHostFree(h);
+            return false;
+        }
+        host = (char *) h;
+        dev = (char *) hd;
+        bytes = n;
+        return true;
+    }
+    void free()
+    {
+        if (host)
+            (void) hipHostFree(host);
+        *this = PinnedBuf();
+    }
+};
+
 struct DevState {
     bool init = false;
     hipStream_t s[2] = {nullptr, nullptr};
@@ -508,9 +533,7 @@ struct DevState {
         hipEvent_t done = nullptr;  // recorded after the launches that read it
     } iov[2];
     uint32_t iov_next = 0;
-    char *bounce = nullptr;     // pinned host: in half + inout half, bounce_half bytes each
-    char *bounce_dev = nullptr; // its device mapping
-    size_t bounce_half = 0;
+    PinnedBuf bounce;           // in half + inout half
     // MPIX_Redop_sync_timing: an event pair around the launch of each of the
     // next t_cap synchronous calls on s[0] (t_used recorded so far)
     std::vector<hipEvent_t> tev;
@@ -524,19 +547,14 @@ struct DevState {
 // busy stages its operands instead (same kernel, same bits).
 struct PipeSlot {
     hipStream_t s = nullptr;
-    char *host = nullptr;   // nbuf buffers of (in half + inout half), half bytes each
-    char *dev = nullptr;    // its device mapping
-    hipEvent_t ev[2] = {nullptr, nullptr};   // kernel of the chunk in buffer 0 / 1 done
+    PinnedBuf buf;          // nbuf buffers of (in half + inout half), half bytes each
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};     // kernel of the chunk in buffer k done
 };
 struct PipeSet {
     std::mutex mu;
-    PipeSlot slot[16];
-    // wave mode: 3 chunk buffers (in half + inout half each), one stream
-    char *ring = nullptr, *ring_dev = nullptr;
-    size_t ring_half = 0;
-    hipStream_t ring_s = nullptr;
-    hipEvent_t ring_ev[3] = {nullptr, nullptr, nullptr};
-    size_t half = 0;        // slot half size; slots [0, threads) hold host != nullptr
+    PipeSlot slot[16];      // one or two buffers each
+    PipeSlot ring;          // wave mode: 3 chunk buffers (in half + inout half each), one stream
+    size_t half = 0;        // slot half size; slots [0, threads) hold buf.host != nullptr
     int nbuf = 0;           // buffers per worker (2: double-buffered)
     bool cpus_known = false;
     std::vector<int> cpus;  // worker CPUs (empty: no pinning)
@@ -726,7 +744,7 @@ int wait_stream(DevState *d, hipStream_t s)
     return hip_err(e);
 }
 
-enum class Where { Device, Pinned, Pageable };
+using Where = mpix::Place;
 
 // Device / managed memory is used in place.  Pinned (page-locked, mapped)
 // host memory is read and written by the kernel directly over PCIe
@@ -798,35 +816,44 @@ int validate(const void *in, const void *io, MPIX_Aint count, uint32_t dt, uint3
     return MPIX_REDOP_SUCCESS;
 }
 
-// Enqueue on a stream; both buffers device-accessible, arguments validated.
-// done/seq (synchronous callers): on success with *signalled set, seq will be
-// stored to *done once the result is complete (Params::done; ctr: its
-// workgroup counter, NULL = one workgroup only).
-int enqueue(const void *in, void *io, uint64_t count, uint32_t it, uint64_t ext, uint32_t op,
-            hipStream_t s, uint32_t *done = nullptr, uint32_t *ctr = nullptr, uint32_t seq = 0,
-            bool *signalled = nullptr, bool zero_copy = false, bool sync = false)
+// The combine to run: validated arguments, both buffers device-accessible.
+struct Combine {
+    const void *in;
+    void *io;
+    uint64_t count;
+    uint32_t it;        // internal type
+    uint64_t ext;       // its extent
+    uint32_t op;
+};
+
+// run_sync's enqueue on the library stream, with its store policy.  prm.done
+// set: on success with *signalled set, prm.done_seq will be stored to it once
+// the result is complete (prm.done_ctr: its workgroup counter).
+int enqueue_sync(const Combine &c, hipStream_t s, bool zero_copy, bool sync, const Params &prm,
+                 bool *signalled)
 {
-    if (signalled)
-        *signalled = false;
-    uint32_t opi = op & 0xf;
+    *signalled = false;
+    uint32_t opi = c.op & 0xf;
     if (opi == kOpNoOp)
         return MPIX_REDOP_SUCCESS;
     if (opi == kOpReplace)      // = MPIR_Localcopy (op_fns.c:445-457)
-        return replace_rows(io, ext, in, ext, count, it, ext, s);
+        return replace_rows(c.io, c.ext, c.in, c.ext, c.count, c.it, c.ext, s);
     if (opi == kOpEqual)        // MPI_BYTE only (opequal.c:22-23)
-        return ((it & 0xffffff00u) == U8 && count >= 8)
-            ? hip_err(mpix::launch_equal(in, io, count, s)) : MPIX_REDOP_ERR_TYPE;
-    const Entry *e = gpu_entry(opi, it);
+        return ((c.it & 0xffffff00u) == U8 && c.count >= 8)
+            ? hip_err(mpix::launch_equal(c.in, c.io, c.count, s)) : MPIX_REDOP_ERR_TYPE;
+    const Entry *e = gpu_entry(opi, c.it);
     if (!e)
         return MPIX_REDOP_ERR_TYPE;
-    Params prm = params();
-    prm.done = done;
-    prm.done_ctr = ctr;
-    prm.done_seq = seq;
-    int rc = hip_err(e->contig(in, io, count, prm, launch_cfg(zero_copy, sync), s));
-    if (signalled)
-        *signalled = done && rc == MPIX_REDOP_SUCCESS;
+    int rc = hip_err(e->contig(c.in, c.io, c.count, prm, launch_cfg(zero_copy, sync), s));
+    *signalled = prm.done && rc == MPIX_REDOP_SUCCESS;
     return rc;
+}
+
+// Enqueue on a stream (zero_copy: an operand is page-locked host memory).
+int enqueue(const Combine &c, hipStream_t s, bool zero_copy = false)
+{
+    bool signalled;
+    return enqueue_sync(c, s, zero_copy, false, params(), &signalled);
 }
 
 // Synchronous combine of device-accessible operands on the library stream.
@@ -835,8 +862,7 @@ int enqueue(const void *in, void *io, uint64_t count, uint32_t it, uint64_t ext,
 // saving the end-of-kernel and stream-packet round trip:
 // profiles/r01_sync_latency.txt); other ops and the other wait modes go
 // through wait_stream.
-int run_sync(DevState *d, const void *in, void *io, uint64_t count, uint32_t it, uint64_t ext,
-             uint32_t op, bool zero_copy = false)
+int run_sync(DevState *d, const Combine &c, bool zero_copy = false)
 {
     launch_cfg();       // environment read before g_sync is consulted
     // timed call (MPIX_Redop_sync_timing): the pair brackets the launch on
@@ -856,84 +882,99 @@ int run_sync(DevState *d, const void *in, void *io, uint64_t count, uint32_t it,
                 (void) hipEventRecord(d->tev[2 * ti + 1], d->s[0]);
         }
     };
+    Params prm = params();
     if (g_sync.load() == 2 && d->flag) {
-        const uint32_t seq = ++d->seq;
-        bool signalled = false;
-        int rc;
-        {
-            Stop stop{d, ti};
-            rc = enqueue(in, io, count, it, ext, op, d->s[0], (uint32_t *) d->flag, d->flag_ctr,
-                         seq, &signalled, zero_copy, true);
-        }
-        if (signalled)      // the kernel stores the word itself
-            return spin_on_flag(d, d->s[0], seq);
-        int rc2 = wait_stream(d, d->s[0]);
-        return rc ? rc : rc2;
+        prm.done = (uint32_t *) d->flag;
+        prm.done_ctr = d->flag_ctr;
+        prm.done_seq = ++d->seq;
     }
+    bool signalled = false;
     int rc;
     {
         Stop stop{d, ti};
-        rc = enqueue(in, io, count, it, ext, op, d->s[0], nullptr, nullptr, 0, nullptr, zero_copy,
-                     true);
+        rc = enqueue_sync(c, d->s[0], zero_copy, true, prm, &signalled);
     }
+    if (signalled)      // the kernel stores the word itself
+        return spin_on_flag(d, d->s[0], prm.done_seq);
     int rc2 = wait_stream(d, d->s[0]);
     return rc ? rc : rc2;
+}
+
+// ------------------------------------------- host-resident operands
+// The forms mpix::host_route picks from.  in_host / io_host: the form copies
+// that operand itself; the other one is device-accessible as given.
+
+// Device scratch of at least `need` bytes.  A smaller buffer is freed once
+// both library streams are idle (work queued on them may still use it).
+bool device_scratch(DevState *d, size_t need)
+{
+    if (d->scratch_bytes >= need)
+        return true;
+    if (d->scratch) {
+        (void) hipStreamSynchronize(d->s[0]);
+        (void) hipStreamSynchronize(d->s[1]);
+        (void) hipFree(d->scratch);
+    }
+    d->scratch = nullptr;
+    d->scratch_bytes = 0;
+    if (hipMalloc(&d->scratch, need) != hipSuccess)
+        return false;
+    d->scratch_bytes = need;
+    return true;
+}
+
+// Copy-in of an operand the kernel will read from `dst`: device memory of
+// in_peer, which `dev` cannot reach (hipMemcpyPeerAsync), or host memory;
+// neither: nothing, the operand is used in place.
+int stage_in(void *dst, const void *src, size_t bytes, int dev, int in_peer, bool host,
+             hipStream_t s)
+{
+    if (in_peer >= 0)
+        return hip_err(hipMemcpyPeerAsync(dst, dev, src, in_peer, bytes, s));
+    if (host)
+        return hip_err(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
+    return MPIX_REDOP_SUCCESS;
+}
+
+// Elements [off, off + n) of c as a form's kernel sees them: an operand the
+// form copied in its half of `buf` (in first), another in place.
+Combine chunk_of(const Combine &c, uint64_t off, uint64_t n, bool in_copied, bool io_copied,
+                 char *buf, size_t half)
+{
+    return Combine{in_copied ? (const void *) buf : (const char *) c.in + off * c.ext,
+                   io_copied ? (void *) (buf + half) : (char *) c.io + off * c.ext,
+                   n, c.it, c.ext, c.op};
 }
 
 // Host-resident operand(s): stream them through device scratch in chunks,
 // alternating two streams so chunk k+1's copies overlap chunk k's kernel.
 // in_peer >= 0: `in` is device memory of that device, which `dev` cannot reach
 // (no peer access): it is streamed the same way with hipMemcpyPeerAsync.
-int staged(const void *in, void *io, uint64_t count, uint32_t it, uint64_t ext, uint32_t op,
-           bool in_host, bool io_host, int dev, int in_peer = -1)
+int staged(DevState *d, const Combine &c, bool in_host, bool io_host, int dev, int in_peer)
 {
-    if (in_peer >= 0)
-        in_host = true;
-    DevState *d = dev_state(dev);
-    if (!d)
-        return MPIX_REDOP_ERR_OTHER;
-    launch_cfg();
-    uint64_t chunk_elems = g_stage_chunk / ext;
+    uint64_t chunk_elems = g_stage_chunk / c.ext;
     if (chunk_elems == 0)
         chunk_elems = 1;
-    if (chunk_elems > count)
-        chunk_elems = count;
-    size_t slot_bytes = (size_t) (chunk_elems * ext + 255) & ~(size_t) 255;
-    size_t need = 4 * slot_bytes;
-    if (d->scratch_bytes < need) {
-        if (d->scratch)
-            (void) hipFree(d->scratch);
-        d->scratch = nullptr;
-        d->scratch_bytes = 0;
-        if (hipMalloc(&d->scratch, need) != hipSuccess)
-            return MPIX_REDOP_ERR_OTHER;
-        d->scratch_bytes = need;
-    }
+    if (chunk_elems > c.count)
+        chunk_elems = c.count;
+    size_t slot_bytes = (size_t) (chunk_elems * c.ext + 255) & ~(size_t) 255;
+    if (!device_scratch(d, 4 * slot_bytes))     // 2 slots x (in chunk + inout chunk)
+        return MPIX_REDOP_ERR_OTHER;
     int rc = MPIX_REDOP_SUCCESS;
-    for (uint64_t off = 0, k = 0; off < count && rc == MPIX_REDOP_SUCCESS; off += chunk_elems, ++k) {
-        uint64_t n = (count - off < chunk_elems) ? count - off : chunk_elems;
+    for (uint64_t off = 0, k = 0; off < c.count && rc == MPIX_REDOP_SUCCESS;
+         off += chunk_elems, ++k) {
+        uint64_t n = (c.count - off < chunk_elems) ? c.count - off : chunk_elems;
         hipStream_t s = d->s[k & 1];
         char *slot = (char *) d->scratch + (k & 1) * 2 * slot_bytes;
-        const char *src_in = (const char *) in + off * ext;
-        char *dst_io = (char *) io + off * ext;
-        const void *kin = src_in;
-        void *kio = dst_io;
-        if (in_peer >= 0) {
-            rc = hip_err(hipMemcpyPeerAsync(slot, dev, src_in, in_peer, n * ext, s));
-            kin = slot;
-        } else if (in_host) {
-            rc = hip_err(hipMemcpyAsync(slot, src_in, n * ext, hipMemcpyHostToDevice, s));
-            kin = slot;
-        }
-        if (rc == MPIX_REDOP_SUCCESS && io_host) {
-            rc = hip_err(hipMemcpyAsync(slot + slot_bytes, dst_io, n * ext,
-                                        hipMemcpyHostToDevice, s));
-            kio = slot + slot_bytes;
-        }
+        char *dst_io = (char *) c.io + off * c.ext;
+        const Combine kc = chunk_of(c, off, n, in_host || in_peer >= 0, io_host, slot, slot_bytes);
+        rc = stage_in(slot, (const char *) c.in + off * c.ext, n * c.ext, dev, in_peer, in_host, s);
         if (rc == MPIX_REDOP_SUCCESS)
-            rc = enqueue(kin, kio, n, it, ext, op, s);
+            rc = stage_in(slot + slot_bytes, dst_io, n * c.ext, dev, -1, io_host, s);
+        if (rc == MPIX_REDOP_SUCCESS)
+            rc = enqueue(kc, s);
         if (rc == MPIX_REDOP_SUCCESS && io_host)
-            rc = hip_err(hipMemcpyAsync(dst_io, kio, n * ext, hipMemcpyDeviceToHost, s));
+            rc = hip_err(hipMemcpyAsync(dst_io, kc.io, n * c.ext, hipMemcpyDeviceToHost, s));
     }
     int rc2 = wait_stream(d, d->s[0]);
     int rc3 = wait_stream(d, d->s[1]);
@@ -945,114 +986,50 @@ int staged(const void *in, void *io, uint64_t count, uint32_t it, uint64_t ext, 
 // is_equal header back (k_equal writes nothing else).  When the scratch
 // cannot be had nothing has been touched and MPI_ERR_TYPE sends the caller to
 // its own op table.
-int equal_whole(const void *in, void *io, uint64_t n, bool in_host, bool io_host, int dev,
-                int in_peer = -1)
+int equal_whole(DevState *d, const Combine &c, bool in_host, bool io_host, int dev, int in_peer)
 {
-    DevState *d = dev_state(dev);
-    if (!d)
-        return MPIX_REDOP_ERR_OTHER;
-    const size_t half = ((size_t) n + 255) & ~(size_t) 255;
-    if (d->scratch_bytes < 2 * half) {
-        if (d->scratch) {
-            (void) hipStreamSynchronize(d->s[0]);
-            (void) hipStreamSynchronize(d->s[1]);
-            (void) hipFree(d->scratch);
-        }
-        d->scratch = nullptr;
-        d->scratch_bytes = 0;
-        if (hipMalloc(&d->scratch, 2 * half) != hipSuccess) {
-            (void) hipGetLastError();
-            return MPIX_REDOP_ERR_TYPE;
-        }
-        d->scratch_bytes = 2 * half;
+    const size_t n = (size_t) c.count;      // MPI_BYTE
+    const size_t half = (n + 255) & ~(size_t) 255;
+    if (!device_scratch(d, 2 * half)) {
+        (void) hipGetLastError();
+        return MPIX_REDOP_ERR_TYPE;
     }
     hipStream_t s = d->s[0];
-    const void *kin = in;
-    void *kio = io;
-    int rc = MPIX_REDOP_SUCCESS;
-    if (in_peer >= 0) {
-        rc = hip_err(hipMemcpyPeerAsync(d->scratch, dev, in, in_peer, n, s));
-        kin = d->scratch;
-    } else if (in_host) {
-        rc = hip_err(hipMemcpyAsync(d->scratch, in, n, hipMemcpyHostToDevice, s));
-        kin = d->scratch;
-    }
-    if (rc == MPIX_REDOP_SUCCESS && io_host) {
-        kio = (char *) d->scratch + half;
-        rc = hip_err(hipMemcpyAsync(kio, io, n, hipMemcpyHostToDevice, s));
-    }
+    char *scratch = (char *) d->scratch;
+    const Combine kc = chunk_of(c, 0, n, in_host || in_peer >= 0, io_host, scratch, half);
+    int rc = stage_in(scratch, c.in, n, dev, in_peer, in_host, s);
     if (rc == MPIX_REDOP_SUCCESS)
-        rc = hip_err(mpix::launch_equal(kin, kio, n, s));
+        rc = stage_in(scratch + half, c.io, n, dev, -1, io_host, s);
+    if (rc == MPIX_REDOP_SUCCESS)
+        rc = hip_err(mpix::launch_equal(kc.in, kc.io, n, s));
     if (rc == MPIX_REDOP_SUCCESS && io_host)
-        rc = hip_err(hipMemcpyAsync(io, kio, 8, hipMemcpyDeviceToHost, s));
+        rc = hip_err(hipMemcpyAsync(c.io, kc.io, 8, hipMemcpyDeviceToHost, s));
     int rc2 = wait_stream(d, s);
     return rc ? rc : rc2;
 }
 
 // Small pageable operand(s): memcpy into the pinned bounce buffer, one
 // zero-copy kernel over it, memcpy the result back (a staged 1-element call
-// costs ~42 us in three pageable hipMemcpy calls).  Returns -1 when the bounce buffer cannot be had (caller stages).
-int bounced(const void *in, void *io, uint64_t count, uint32_t it, uint64_t ext, uint32_t op,
-            bool in_host, bool io_host, int dev)
+// costs ~42 us in three pageable hipMemcpy calls).
+// Returns -1 when the bounce buffer cannot be had (caller stages).
+int bounced(DevState *d, const Combine &c, bool in_host, bool io_host)
 {
-    DevState *d = dev_state(dev);
-    if (!d)
-        return MPIX_REDOP_ERR_OTHER;
-    size_t bytes = (size_t) (count * ext);
-    if (!d->bounce) {
-        void *h = nullptr, *hd = nullptr;
-        size_t half = (g_bounce_bytes + 255) & ~(size_t) 255;
-        if (hipHostMalloc(&h, 2 * half, hipHostMallocDefault) != hipSuccess)
-            return -1;
-        if (hipHostGetDevicePointer(&hd, h, 0) != hipSuccess) {
-            (void) hipHostFree(h);
-            return -1;
-        }
-        d->bounce = (char *) h;
-        d->bounce_dev = (char *) hd;
-        d->bounce_half = half;
-    }
-    if (bytes > d->bounce_half)
+    size_t bytes = (size_t) (c.count * c.ext);
+    if (!d->bounce.host && !d->bounce.alloc(2 * ((g_bounce_bytes + 255) & ~(size_t) 255)))
         return -1;
-    const void *kin = in;
-    void *kio = io;
-    if (in_host) {
-        memcpy(d->bounce, in, bytes);
-        kin = d->bounce_dev;
-    }
-    if (io_host) {
-        memcpy(d->bounce + d->bounce_half, io, bytes);
-        kio = d->bounce_dev + d->bounce_half;
-    }
-    int rc = run_sync(d, kin, kio, count, it, ext, op, true);
+    const size_t half = d->bounce.bytes / 2;
+    if (bytes > half)
+        return -1;
+    if (in_host)
+        memcpy(d->bounce.host, c.in, bytes);
+    if (io_host)
+        memcpy(d->bounce.host + half, c.io, bytes);
+    int rc = run_sync(d, chunk_of(c, 0, c.count, in_host, io_host, d->bounce.dev, half), true);
     if (rc == MPIX_REDOP_SUCCESS && io_host)
-        memcpy(io, d->bounce + d->bounce_half, bytes);
+        memcpy(c.io, d->bounce.host + half, bytes);
     return rc;
 }
 
-// Host workers for one pageable call: the configured count, at most one per
-// CPU this process may run on (more would only take turns on the same cores).
-int worker_count(int nthreads)
-{
-    int w = nthreads < 1 ? 1 : nthreads;
-    cpu_set_t mine;
-    if (sched_getaffinity(0, sizeof mine, &mine) == 0) {
-        const int cpus = CPU_COUNT(&mine);
-        if (cpus >= 1 && w > cpus)
-            w = cpus;
-    }
-    return w;
-}
-
-// Large pageable operand(s): W host workers take chunks k = w, w + W, ...; per
-// chunk a worker memcpys the pageable operand(s) into its pinned slot, runs one
-// zero-copy kernel over the slot's device mapping on its own stream (a pinned
-// or device operand is used in place), waits for it and memcpys the result
-// back.  The workers' host copies overlap each other's PCIe transfers, where
-// hipMemcpyAsync from pageable memory serialises through the runtime's own
-// bounce.  Each element is combined exactly once, by the same kernel, so the
-// bits equal every other path's.  Returns -1 when the slots cannot be had
-// (caller stages).
 // Copy into a pinned buffer the GPU is about to read over PCIe.  With plain
 // stores the lines sit dirty in the CPU caches and every PCIe read of them is
 // a snoop hit; non-temporal stores send them to DRAM (glibc's memcpy switches
@@ -1097,43 +1074,14 @@ void copy_to_pinned(char *dst, const char *src, size_t n)
         memcpy(dst, src, n);
 }
 
-struct PipeTrace {
-    int64_t *ns;        // 5 per chunk, or nullptr
-    std::chrono::steady_clock::time_point t0;
-};
-inline void pipe_mark(PipeTrace *t, int, uint64_t k, int what)
+// The workers' CPUs, found once per device: those of the GPU's NUMA node
+// (sysfs local_cpulist of its PCI function) or an explicit "a-b,c" list,
+// intersected with this process's affinity; empty: no pinning
+const std::vector<int> &worker_cpus(PipeSet &P, int dev)
 {
-    if (t->ns)
-        t->ns[k * 5 + (uint64_t) what] = std::chrono::duration_cast<std::chrono::nanoseconds>(
-                                             std::chrono::steady_clock::now() - t->t0).count();
-}
-
-// CPUs of the GPU's NUMA node (sysfs local_cpulist of its PCI function),
-// intersected with this process's affinity; or an explicit "a-b,c" list
-std::vector<int> parse_cpulist(const char *txt)
-{
-    std::vector<int> out;
-    for (const char *p = txt; *p;) {
-        char *e;
-        long a = strtol(p, &e, 10);
-        if (e == p)
-            break;
-        long b = a;
-        p = e;
-        if (*p == '-') {
-            b = strtol(p + 1, &e, 10);
-            p = e;
-        }
-        for (long c = a; c <= b && c < 4096; ++c)
-            out.push_back((int) c);
-        while (*p == ',' || *p == ' ' || *p == '\n')
-            ++p;
-    }
-    return out;
-}
-
-std::vector<int> worker_cpus(int dev)
-{
+    if (P.cpus_known)
+        return P.cpus;
+    P.cpus_known = true;
     std::vector<int> want;
     const std::string mode = g_pipe_affinity;
     if (mode == "gpu") {
@@ -1145,22 +1093,21 @@ std::vector<int> worker_cpus(int dev)
             if (FILE *f = fopen(path.c_str(), "r")) {
                 char line[4096] = {0};
                 if (fgets(line, sizeof line, f))
-                    want = parse_cpulist(line);
+                    want = mpix::parse_cpulist(line);
                 fclose(f);
             }
         }
         (void) hipGetLastError();
     } else if (mode != "none" && !mode.empty()) {
-        want = parse_cpulist(mode.c_str());
+        want = mpix::parse_cpulist(mode.c_str());
     }
     cpu_set_t mine;
-    std::vector<int> out;
     if (want.empty() || sched_getaffinity(0, sizeof mine, &mine) != 0)
-        return out;
+        return P.cpus;
     for (int c : want)
         if (c < CPU_SETSIZE && CPU_ISSET(c, &mine))
-            out.push_back(c);
-    return out;
+            P.cpus.push_back(c);
+    return P.cpus;
 }
 
 // Large pageable operand(s): W host workers take chunks k = w, w + W, ...; per
@@ -1174,8 +1121,7 @@ std::vector<int> worker_cpus(int dev)
 // bounce.  Each element is combined exactly once, by the same kernel, so the
 // bits equal every other path's.  Returns -1 when the buffers cannot be had
 // (caller stages).
-int pipelined(const void *in, void *io, uint64_t count, uint32_t it, uint64_t ext, uint32_t op,
-              bool in_pg, bool io_pg, int dev, int nthreads)
+int pipelined(const Combine &c, bool in_pg, bool io_pg, int dev, int nthreads)
 {
     if (dev < 0 || dev >= kMaxDev)
         return -1;
@@ -1187,15 +1133,13 @@ int pipelined(const void *in, void *io, uint64_t count, uint32_t it, uint64_t ex
     const int nbuf = g_pipe_db.load() ? 2 : 1;
     bool ready = P.half >= half && P.nbuf >= nbuf;
     for (int w = 0; ready && w < nthreads; ++w)
-        ready = P.slot[w].host != nullptr;
+        ready = P.slot[w].buf.host != nullptr;
     if (!ready) {
         // (re)allocate every worker's buffers at the current chunk size
         for (PipeSlot &sl : P.slot) {
             if (sl.s)
                 (void) hipStreamSynchronize(sl.s);
-            if (sl.host)
-                (void) hipHostFree(sl.host);
-            sl.host = sl.dev = nullptr;
+            sl.buf.free();
         }
         P.half = 0;
         P.nbuf = 0;
@@ -1203,82 +1147,62 @@ int pipelined(const void *in, void *io, uint64_t count, uint32_t it, uint64_t ex
             PipeSlot &sl = P.slot[w];
             if (!sl.s && hipStreamCreateWithFlags(&sl.s, hipStreamNonBlocking) != hipSuccess)
                 return -1;
-            for (hipEvent_t &e : sl.ev)
-                if (!e && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess)
+            for (hipEvent_t *e = sl.ev; e < sl.ev + 2; ++e)
+                if (!*e && hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess)
                     return -1;
-            void *h = nullptr, *hd = nullptr;
-            if (hipHostMalloc(&h, 2 * half * (size_t) nbuf, hipHostMallocDefault) != hipSuccess)
+            if (!sl.buf.alloc(2 * half * (size_t) nbuf))
                 return -1;
-            if (hipHostGetDevicePointer(&hd, h, 0) != hipSuccess) {
-                (void) hipHostFree(h);
-                return -1;
-            }
-            sl.host = (char *) h;
-            sl.dev = (char *) hd;
         }
         P.half = half;
         P.nbuf = nbuf;
     }
-    if (!P.cpus_known) {
-        P.cpus = worker_cpus(dev);
-        P.cpus_known = true;
-    }
-    uint64_t chunk = half / ext;
+    const std::vector<int> &cpus = worker_cpus(P, dev);
+    const uint64_t chunk = half / c.ext;
     if (chunk == 0)
         return -1;
-    const uint64_t nchunks = (count + chunk - 1) / chunk;
-    const int W = (int) std::min<uint64_t>((uint64_t) worker_count(nthreads), nchunks);
-    std::atomic<int> err{MPIX_REDOP_SUCCESS};
+    const uint64_t nchunks = (c.count + chunk - 1) / chunk;
+    const int W = (int) std::min<uint64_t>((uint64_t) mpix::worker_count(nthreads), nchunks);
+    mpix::FirstError err;
     // MPIX_REDOP_PIPE_TRACE=1: per chunk the host times (ns from the call's
     // start) of copy-in start / end, wait start / end, copy-out end, printed
     // as one JSON line to stderr (tools/pageable_probe.py reads them)
-    static const bool trace_on = getenv("MPIX_REDOP_PIPE_TRACE") != nullptr;
-    std::vector<int64_t> trace_buf(trace_on ? nchunks * 5 : 0, -1);
-    PipeTrace trv{trace_on ? trace_buf.data() : nullptr, std::chrono::steady_clock::now()};
-    PipeTrace *tr = &trv;
-    auto fail = [&](int rc) {
-        int z = MPIX_REDOP_SUCCESS;
-        err.compare_exchange_strong(z, rc);
-    };
+    mpix::StepTrace tr(nchunks);
     auto work = [&](int w) {
         PipeSlot &sl = P.slot[w];
         if (hipSetDevice(dev) != hipSuccess) {
-            fail(MPIX_REDOP_ERR_OTHER);
+            err.fail(MPIX_REDOP_ERR_OTHER);
             return;
         }
-        char *hbuf[2] = {sl.host, sl.host + 2 * half};
-        char *dbuf[2] = {sl.dev, sl.dev + 2 * half};
+        char *hbuf[2] = {sl.buf.host, sl.buf.host + 2 * half};
+        char *dbuf[2] = {sl.buf.dev, sl.buf.dev + 2 * half};
         // buffer b: copy chunk k's pageable operand(s) in, enqueue its kernel
         auto start = [&](uint64_t k, int b) -> int {
-            const uint64_t off = k * chunk, n = std::min(chunk, count - off);
-            const size_t bytes = (size_t) (n * ext);
-            pipe_mark(tr, w, k, 0);
+            const uint64_t off = k * chunk, n = std::min(chunk, c.count - off);
+            const size_t bytes = (size_t) (n * c.ext);
+            tr.mark(k, 0);
             if (in_pg)
-                copy_to_pinned(hbuf[b], (const char *) in + off * ext, bytes);
+                copy_to_pinned(hbuf[b], (const char *) c.in + off * c.ext, bytes);
             if (io_pg)
-                copy_to_pinned(hbuf[b] + half, (char *) io + off * ext, bytes);
-            pipe_mark(tr, w, k, 1);
-            const void *kin = in_pg ? (const void *) dbuf[b] : (const char *) in + off * ext;
-            void *kio = io_pg ? (void *) (dbuf[b] + half) : (char *) io + off * ext;
-            int rc = enqueue(kin, kio, n, it, ext, op, sl.s, nullptr, nullptr, 0, nullptr, true);
+                copy_to_pinned(hbuf[b] + half, (char *) c.io + off * c.ext, bytes);
+            tr.mark(k, 1);
+            int rc = enqueue(chunk_of(c, off, n, in_pg, io_pg, dbuf[b], half), sl.s, true);
             return rc ? rc : hip_err(hipEventRecord(sl.ev[b], sl.s));
         };
         // chunk k's kernel done: its result back to the pageable inout
         auto finish = [&](uint64_t k, int b) -> int {
-            pipe_mark(tr, w, k, 2);
+            tr.mark(k, 2);
             int rc = hip_err(hipEventSynchronize(sl.ev[b]));
-            pipe_mark(tr, w, k, 3);
+            tr.mark(k, 3);
             if (rc == MPIX_REDOP_SUCCESS && io_pg) {
-                const uint64_t off = k * chunk, n = std::min(chunk, count - off);
-                memcpy((char *) io + off * ext, hbuf[b] + half, (size_t) (n * ext));
+                const uint64_t off = k * chunk, n = std::min(chunk, c.count - off);
+                memcpy((char *) c.io + off * c.ext, hbuf[b] + half, (size_t) (n * c.ext));
             }
-            pipe_mark(tr, w, k, 4);
+            tr.mark(k, 4);
             return rc;
         };
         uint64_t k = (uint64_t) w;
         int b = 0, rc = k < nchunks ? start(k, b) : MPIX_REDOP_SUCCESS;
-        for (; k < nchunks && rc == MPIX_REDOP_SUCCESS && err.load() == MPIX_REDOP_SUCCESS;
-             k += (uint64_t) W) {
+        for (; k < nchunks && rc == MPIX_REDOP_SUCCESS && err.ok(); k += (uint64_t) W) {
             const uint64_t kn = k + (uint64_t) W;
             if (nbuf == 2) {
                 if (kn < nchunks)
@@ -1295,78 +1219,15 @@ int pipelined(const void *in, void *io, uint64_t count, uint32_t it, uint64_t ex
         // no kernel of this worker is left reading its buffers when the call
         // returns, also when another worker's failure ended the loop early
         (void) hipStreamSynchronize(sl.s);
-        if (rc != MPIX_REDOP_SUCCESS)
-            fail(rc);
+        err.fail(rc);
     };
-    std::vector<std::thread> pool;
-    pool.reserve(W > 0 ? W - 1 : 0);
-    for (int w = 1; w < W; ++w)
-        pool.emplace_back([&, w]() {
-            if (!P.cpus.empty()) {
-                cpu_set_t set;
-                CPU_ZERO(&set);
-                CPU_SET(P.cpus[(size_t) w % P.cpus.size()], &set);
-                (void) pthread_setaffinity_np(pthread_self(), sizeof set, &set);
-            }
-            work(w);
-        });
-    work(0);        // the caller is worker 0 (its affinity is its own)
-    for (std::thread &t : pool)
-        t.join();
-    if (trace_on) {
-        fprintf(stderr, "{\"pipe_trace\": {\"W\": %d, \"chunk\": %zu, \"nbuf\": %d, \"ns\": [", W,
-                half, nbuf);
-        for (uint64_t i = 0; i < nchunks * 5; ++i)
-            fprintf(stderr, "%s%lld", i ? "," : "", (long long) trace_buf[i]);
-        fprintf(stderr, "]}}\n");
+    mpix::run_workers(W, cpus, work);
+    if (tr.on) {
+        fprintf(stderr, "{\"pipe_trace\": {\"W\": %d, \"chunk\": %zu, \"nbuf\": %d, ", W, half, nbuf);
+        tr.print_ns(stderr);
     }
-    return err.load();
+    return err.rc.load();
 }
-
-// Barrier of the wave workers (sense reversal).  A waiter spins with `pause`
-// for up to kSpinNs, then sleeps on a futex on the generation word until the
-// last worker arrives and wakes it.  Not a yield loop: a yielding waiter on a
-// CPU shared with other runnable tasks can be left off it for a whole
-// scheduler slice, and every step waits for the last worker to leave -- one
-// such stall took a 256 MiB call from 12.6 to 21 ms
-// (profiles/r04_pageable_swing.json, the slowest trace's step 7).  Not a long
-// spin either: with fewer cores than workers, spinning waiters
-// would keep the worker they wait for off the core.  The steps' own imbalance
-// is well under the spin window, so a balanced wave never sleeps.
-struct SpinBarrier {
-    static constexpr int64_t kSpinNs = 200000;
-    std::atomic<int> left;
-    std::atomic<int> gen{0};
-    std::atomic<int> sleepers{0};
-    const int n;
-    explicit SpinBarrier(int n_) : left(n_), n(n_) {}
-    void wait()
-    {
-        const int g = gen.load();
-        if (left.fetch_sub(1) == 1) {
-            left.store(n);
-            gen.fetch_add(1);           // seq_cst: ordered before the sleepers check
-            if (sleepers.load() > 0)
-                syscall(SYS_futex, reinterpret_cast<int *>(&gen), FUTEX_WAKE_PRIVATE, INT32_MAX,
-                        nullptr, nullptr, 0);
-            return;
-        }
-        const auto t0 = std::chrono::steady_clock::now();
-        for (uint32_t spins = 1; gen.load(std::memory_order_acquire) == g; ++spins) {
-            _mm_pause();
-            if ((spins & 0xff) == 0 &&
-                std::chrono::steady_clock::now() - t0 > std::chrono::nanoseconds(kSpinNs))
-                break;
-        }
-        if (gen.load() != g)
-            return;
-        sleepers.fetch_add(1);          // seq_cst: the releaser sees it, or we see its gen
-        while (gen.load() == g)
-            syscall(SYS_futex, reinterpret_cast<int *>(&gen), FUTEX_WAIT_PRIVATE, g, nullptr,
-                    nullptr, 0);
-        sleepers.fetch_sub(1);
-    }
-};
 
 // Wave mode (see g_pipe_wave).  Step s: the caller launches the kernel of
 // chunk s - 1 (its copy-in finished in step s - 1); every worker copies its
@@ -1374,8 +1235,7 @@ struct SpinBarrier {
 // chunk s - 2 out; then all meet.  Buffer s % 3 held chunk s - 3, whose
 // copy-out ended in step s - 1.  Same kernel per element, same bits.
 // Returns -1 when the buffers cannot be had (caller stages).
-int waved(const void *in, void *io, uint64_t count, uint32_t it, uint64_t ext, uint32_t op,
-          bool in_pg, bool io_pg, int dev, int nthreads)
+int waved(const Combine &c, bool in_pg, bool io_pg, int dev, int nthreads)
 {
     if (dev < 0 || dev >= kMaxDev)
         return -1;
@@ -1384,107 +1244,57 @@ int waved(const void *in, void *io, uint64_t count, uint32_t it, uint64_t ext, u
     if (!busy.owns_lock())
         return -1;
     const size_t half = (g_pipe_chunk.load() + 255) & ~(size_t) 255;
-    if (P.ring_half < half) {
-        if (P.ring_s)
-            (void) hipStreamSynchronize(P.ring_s);
-        if (P.ring)
-            (void) hipHostFree(P.ring);
-        P.ring = P.ring_dev = nullptr;
-        P.ring_half = 0;
-        if (!P.ring_s && hipStreamCreateWithFlags(&P.ring_s, hipStreamNonBlocking) != hipSuccess)
+    if (P.ring.buf.bytes < 6 * half) {
+        if (P.ring.s)
+            (void) hipStreamSynchronize(P.ring.s);
+        P.ring.buf.free();
+        if (!P.ring.s && hipStreamCreateWithFlags(&P.ring.s, hipStreamNonBlocking) != hipSuccess)
             return -1;
-        for (hipEvent_t &e : P.ring_ev)
+        for (hipEvent_t &e : P.ring.ev)
             if (!e && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess)
                 return -1;
-        void *h = nullptr, *hd = nullptr;
-        if (hipHostMalloc(&h, 3 * 2 * half, hipHostMallocDefault) != hipSuccess)
+        if (!P.ring.buf.alloc(3 * 2 * half))
             return -1;
-        if (hipHostGetDevicePointer(&hd, h, 0) != hipSuccess) {
-            (void) hipHostFree(h);
-            return -1;
-        }
-        P.ring = (char *) h;
-        P.ring_dev = (char *) hd;
-        P.ring_half = half;
     }
-    if (!P.cpus_known) {
-        P.cpus = worker_cpus(dev);
-        P.cpus_known = true;
-    }
-    const uint64_t chunk = half / ext;
+    const std::vector<int> &cpus = worker_cpus(P, dev);
+    const uint64_t chunk = half / c.ext;
     if (chunk == 0)
         return -1;
-    // chunk sizes ramp up (chunk/8, /4, /2) so the first kernel starts after a
-    // short copy-in, and down again at the end so the last copy-out is short;
-    // full chunks in between.  Offsets and counts in elements.
-    std::vector<std::pair<uint64_t, uint64_t>> chunks;
-    {
-        uint64_t off = 0;
-        for (int r = 3; r >= 1 && off < count; --r) {
-            const uint64_t c = std::max<uint64_t>(chunk >> r, 1);
-            const uint64_t m = std::min(c, count - off);
-            chunks.emplace_back(off, m);
-            off += m;
-        }
-        const uint64_t tail_split = chunk;      // the last full chunk's worth goes in halves
-        while (count - off > chunk + tail_split) {
-            chunks.emplace_back(off, chunk);
-            off += chunk;
-        }
-        for (int r = 1; off < count; r = r < 3 ? r + 1 : 3) {
-            const uint64_t c = std::max<uint64_t>(chunk >> r, 1);
-            const uint64_t m = (count - off <= c || r == 3) ? std::min(count - off, chunk) : c;
-            chunks.emplace_back(off, m);
-            off += m;
-        }
-    }
+    // offsets and counts in elements, no chunk above a ring half
+    const std::vector<mpix::Chunk> chunks = mpix::wave_chunks(c.count, chunk);
     const int64_t n = (int64_t) chunks.size();
-    const int W = worker_count(nthreads);
-    SpinBarrier bar(W);
+    const int W = mpix::worker_count(nthreads);
+    mpix::SpinBarrier bar(W);
     // MPIX_REDOP_PIPE_TRACE=1: per step and worker the host times (ns from the
     // call's start) at which the kernel launch (worker 0), the copy-in, the
     // wait for the kernel of chunk st - 2, its copy-out and the step's barrier
     // ended, and the CPU each worker started on -- one JSON line to stderr
     // (tools/pageable_swing.py reads it)
-    static const bool trace_on = getenv("MPIX_REDOP_PIPE_TRACE") != nullptr;
-    std::vector<int64_t> trace((size_t) (trace_on ? (n + 2) * W * 5 : 0), -1);
-    std::vector<int> trace_cpu((size_t) (trace_on ? W : 0), -1);
-    const auto t0 = std::chrono::steady_clock::now();
+    mpix::StepTrace tr((size_t) (n + 2) * (size_t) W);
+    std::vector<int> trace_cpu((size_t) (tr.on ? W : 0), -1);
     auto mark = [&](int64_t st, int w, int what) {
-        if (trace_on)
-            trace[((size_t) st * (size_t) W + (size_t) w) * 5 + (size_t) what] =
-                std::chrono::duration_cast<std::chrono::nanoseconds>(
-                    std::chrono::steady_clock::now() - t0).count();
+        tr.mark((size_t) st * (size_t) W + (size_t) w, what);
     };
-    std::atomic<int> err{MPIX_REDOP_SUCCESS};
-    auto fail = [&](int rc) {
-        int z = MPIX_REDOP_SUCCESS;
-        err.compare_exchange_strong(z, rc);
+    mpix::FirstError err;
+    // chunk k, copied into buffer b, as its kernel sees it
+    auto kernel_chunk = [&](int64_t k, int b) {
+        return chunk_of(c, chunks[(size_t) k].off, chunks[(size_t) k].count, in_pg, io_pg,
+                        P.ring.buf.dev + (size_t) b * 2 * half, half);
     };
-    auto span = [&](int64_t k, uint64_t *off, uint64_t *cnt) {
-        *off = chunks[(size_t) k].first;
-        *cnt = chunks[(size_t) k].second;
-    };
-    // worker w's slice of a chunk of `bytes`: 4 KiB-aligned parts
-    auto slice = [&](int w, size_t bytes, size_t *lo, size_t *len) {
-        size_t per = ((bytes + (size_t) W - 1) / (size_t) W + 4095) & ~(size_t) 4095;
-        *lo = std::min(bytes, per * (size_t) w);
-        *len = std::min(bytes - *lo, per);
+    // worker w's slice of chunk k: its offset in the operands, in the chunk, its length
+    auto part = [&](int64_t k, int w, size_t *at, size_t *lo, size_t *len) {
+        *at = (size_t) (chunks[(size_t) k].off * c.ext);
+        mpix::slice(w, W, (size_t) (chunks[(size_t) k].count * c.ext), lo, len);
     };
     auto work = [&](int w) {
-        if (trace_on)
+        if (tr.on)
             trace_cpu[(size_t) w] = sched_getcpu();
         if (hipSetDevice(dev) != hipSuccess) {
-            fail(MPIX_REDOP_ERR_OTHER);
+            err.fail(MPIX_REDOP_ERR_OTHER);
         }
         for (int64_t st = 0; st <= n + 1; ++st) {
-            if (w == 0 && st >= 1 && st - 1 < n && err.load() == MPIX_REDOP_SUCCESS) {
-                uint64_t off, cnt;
-                span(st - 1, &off, &cnt);
+            if (w == 0 && st >= 1 && st - 1 < n && err.ok()) {
                 const int b = (int) ((st - 1) % 3);
-                char *d = P.ring_dev + (size_t) b * 2 * half;
-                const void *kin = in_pg ? (const void *) d : (const char *) in + off * ext;
-                void *kio = io_pg ? (void *) (d + half) : (char *) io + off * ext;
                 // one stream for all chunks: kernels of consecutive chunks on
                 // three streams, overlapping each other's ramp, measured 25 %
                 // slower (57.5 vs 46.1 ms per 1 GiB; zero-copy kernels
@@ -1497,40 +1307,34 @@ int waved(const void *in, void *io, uint64_t count, uint32_t it, uint64_t ext, u
                 // (profiles/r03_pageable_split_rejected.jsonl): the copy
                 // engine and the CUs' PCIe reads share the link badly, as the
                 // SDMA-only duplex pattern does (56 ms, bench.py pcie)
-                int rc = enqueue(kin, kio, cnt, it, ext, op, P.ring_s, nullptr, nullptr, 0, nullptr,
-                                 true);
+                int rc = enqueue(kernel_chunk(st - 1, b), P.ring.s, true);
                 if (rc == MPIX_REDOP_SUCCESS)
-                    rc = hip_err(hipEventRecord(P.ring_ev[b], P.ring_s));
-                if (rc)
-                    fail(rc);
+                    rc = hip_err(hipEventRecord(P.ring.ev[b], P.ring.s));
+                err.fail(rc);
                 mark(st, w, 0);
             }
-            if (st < n && err.load() == MPIX_REDOP_SUCCESS) {       // copy chunk st in
-                uint64_t off, cnt;
-                span(st, &off, &cnt);
-                char *h = P.ring + (size_t) (st % 3) * 2 * half;
-                size_t lo, len;
-                slice(w, (size_t) (cnt * ext), &lo, &len);
+            if (st < n && err.ok()) {       // copy chunk st in
+                char *h = P.ring.buf.host + (size_t) (st % 3) * 2 * half;
+                size_t at, lo, len;
+                part(st, w, &at, &lo, &len);
                 if (len && in_pg)
-                    copy_to_pinned(h + lo, (const char *) in + off * ext + lo, len);
+                    copy_to_pinned(h + lo, (const char *) c.in + at + lo, len);
                 if (len && io_pg)
-                    copy_to_pinned(h + half + lo, (const char *) io + off * ext + lo, len);
+                    copy_to_pinned(h + half + lo, (const char *) c.io + at + lo, len);
                 mark(st, w, 1);
             }
-            if (st >= 2 && st - 2 < n && err.load() == MPIX_REDOP_SUCCESS) {   // chunk st-2 out
+            if (st >= 2 && st - 2 < n && err.ok()) {   // chunk st-2 out
                 const int b = (int) ((st - 2) % 3);
-                int rc = hip_err(hipEventSynchronize(P.ring_ev[b]));
+                int rc = hip_err(hipEventSynchronize(P.ring.ev[b]));
                 mark(st, w, 2);
                 if (rc)
-                    fail(rc);
+                    err.fail(rc);
                 else if (io_pg) {
-                    uint64_t off, cnt;
-                    span(st - 2, &off, &cnt);
-                    size_t lo, len;
-                    slice(w, (size_t) (cnt * ext), &lo, &len);
+                    size_t at, lo, len;
+                    part(st - 2, w, &at, &lo, &len);
                     if (len)
-                        memcpy((char *) io + off * ext + lo, P.ring + (size_t) b * 2 * half + half + lo,
-                               len);
+                        memcpy((char *) c.io + at + lo,
+                               P.ring.buf.host + (size_t) b * 2 * half + half + lo, len);
                 }
                 mark(st, w, 3);
             }
@@ -1538,36 +1342,20 @@ int waved(const void *in, void *io, uint64_t count, uint32_t it, uint64_t ext, u
             mark(st, w, 4);
         }
     };
-    std::vector<std::thread> pool;
-    pool.reserve((size_t) W - 1);
-    for (int w = 1; w < W; ++w)
-        pool.emplace_back([&, w]() {
-            if (!P.cpus.empty()) {
-                cpu_set_t set;
-                CPU_ZERO(&set);
-                CPU_SET(P.cpus[(size_t) w % P.cpus.size()], &set);
-                (void) pthread_setaffinity_np(pthread_self(), sizeof set, &set);
-            }
-            work(w);
-        });
-    work(0);
-    for (std::thread &t : pool)
-        t.join();
-    (void) hipStreamSynchronize(P.ring_s);      // nothing left reading the buffers
-    if (trace_on) {
+    mpix::run_workers(W, cpus, work);
+    (void) hipStreamSynchronize(P.ring.s);      // nothing left reading the buffers
+    if (tr.on) {
         fprintf(stderr, "{\"wave_trace\": {\"W\": %d, \"ext\": %llu, \"chunks\": [", W,
-                (unsigned long long) ext);
+                (unsigned long long) c.ext);
         for (int64_t k = 0; k < n; ++k)
-            fprintf(stderr, "%s%llu", k ? "," : "", (unsigned long long) chunks[(size_t) k].second);
+            fprintf(stderr, "%s%llu", k ? "," : "", (unsigned long long) chunks[(size_t) k].count);
         fprintf(stderr, "], \"cpus\": [");
         for (int w = 0; w < W; ++w)
             fprintf(stderr, "%s%d", w ? "," : "", trace_cpu[(size_t) w]);
-        fprintf(stderr, "], \"ns\": [");
-        for (size_t i = 0; i < trace.size(); ++i)
-            fprintf(stderr, "%s%lld", i ? "," : "", (long long) trace[i]);
-        fprintf(stderr, "]}}\n");
+        fprintf(stderr, "], ");
+        tr.print_ns(stderr);
     }
-    return err.load();
+    return err.rc.load();
 }
 
 struct DeviceGuard {
@@ -2059,8 +1847,7 @@ static void free_states(DevState *arr)
             if (sl.host)
                 (void) hipHostFree(sl.host);
         }
-        if (d.bounce)
-            (void) hipHostFree(d.bounce);
+        d.bounce.free();
         for (hipEvent_t e : d.tev)
             (void) hipEventDestroy(e);
         d = DevState();
@@ -2084,10 +1871,11 @@ int MPIX_Redop_finalize(void)
     for (int i = 0; i < kMaxDev; ++i) {     // the process-wide pageable worker slots
         PipeSet &P = g_pipes[i];
         std::lock_guard<std::mutex> l(P.mu);
-        if (!P.slot[0].s && !P.slot[0].host && !P.ring && !P.ring_s)
+        if (!P.slot[0].s && !P.slot[0].buf.host && !P.ring.buf.host && !P.ring.s)
             continue;
         DeviceGuard g(i);
-        for (PipeSlot &sl : P.slot) {
+        // a slot's stream (synchronised first), its events and its pinned buffer
+        auto release = [](PipeSlot &sl) {
             if (sl.s) {
                 (void) hipStreamSynchronize(sl.s);
                 (void) hipStreamDestroy(sl.s);
@@ -2095,26 +1883,14 @@ int MPIX_Redop_finalize(void)
             for (hipEvent_t e : sl.ev)
                 if (e)
                     (void) hipEventDestroy(e);
-            if (sl.host)
-                (void) hipHostFree(sl.host);
+            sl.buf.free();
             sl = PipeSlot();
-        }
+        };
+        for (PipeSlot &sl : P.slot)
+            release(sl);
         P.half = 0;
         P.nbuf = 0;
-        if (P.ring_s) {
-            (void) hipStreamSynchronize(P.ring_s);
-            (void) hipStreamDestroy(P.ring_s);
-        }
-        for (hipEvent_t &e : P.ring_ev)
-            if (e) {
-                (void) hipEventDestroy(e);
-                e = nullptr;
-            }
-        if (P.ring)
-            (void) hipHostFree(P.ring);
-        P.ring = P.ring_dev = nullptr;
-        P.ring_half = 0;
-        P.ring_s = nullptr;
+        release(P.ring);
     }
     return MPIX_REDOP_SUCCESS;
 }
@@ -2133,8 +1909,8 @@ int MPIX_Reduce_local_async(const void *inbuf, void *inoutbuf, MPIX_Aint count,
     if (!reachable(inbuf, (hipStream_t) stream, &launch, &pin, &zc) ||
         !reachable(inoutbuf, (hipStream_t) stream, &launch, &pio, &zc))
         return set_err(MPIX_REDOP_ERR_BUFFER);
-    return set_err(enqueue(pin, (void *) pio, (uint64_t) count, it, ext, (uint32_t) op,
-                           (hipStream_t) stream, nullptr, nullptr, 0, nullptr, zc));
+    return set_err(enqueue(Combine{pin, (void *) pio, (uint64_t) count, it, ext, (uint32_t) op},
+                           (hipStream_t) stream, zc));
 }
 
 // Several ready chunks in one launch (include/mpix_redop.h).  Checks first,
@@ -2203,8 +1979,8 @@ int MPIX_Reduce_local_batch_async(const void *const *inbufs, void *const *inoutb
     int nd = 0;
     for (int i = 0; i < m; ++i) {
         if (!e || zc[i]) {
-            int rc = enqueue(pin[i], pio[i], cnt[i], it, ext, (uint32_t) op, (hipStream_t) stream,
-                             nullptr, nullptr, 0, nullptr, zc[i]);
+            int rc = enqueue(Combine{pin[i], pio[i], cnt[i], it, ext, (uint32_t) op},
+                             (hipStream_t) stream, zc[i]);
             if (rc != MPIX_REDOP_SUCCESS)
                 return set_err(rc);
             continue;
@@ -2236,57 +2012,46 @@ int MPIX_Reduce_local(const void *inbuf, void *inoutbuf, MPIX_Aint count, MPIX_D
     const void *pin, *pio;
     Where win = classify(inbuf, &din, &pin);
     Where wio = classify(inoutbuf, &dio, &pio);
-    bool zc = g_zero_copy.load();
-    bool in_stage = win == Where::Pageable || (win == Where::Pinned && !zc);
-    bool io_stage = wio == Where::Pageable || (wio == Where::Pinned && !zc);
     int dev = wio == Where::Device ? dio : (win == Where::Device ? din : cur);
     DeviceGuard guard(dev);
-    if (win == Where::Device && wio == Where::Device && din != dio &&
-        peer_state(dio, din) == kPeerNone)
-        // operands on two devices without peer access: the kernel runs where
-        // inout lives and `in` is copied over in chunks (hipMemcpyPeerAsync);
-        // MPIX_EQUAL's one header covers the whole message: copied whole
-        return set_err(opi == kOpEqual
-                           ? equal_whole(pin, (void *) pio, (uint64_t) count, false, false, dev, din)
-                           : staged(pin, (void *) pio, (uint64_t) count, it, ext, (uint32_t) op,
-                                    false, false, dev, din));
-    bool pageable = win == Where::Pageable || wio == Where::Pageable;
-    if (pageable && (uint64_t) count * ext <= g_bounce_bytes) {
-        // only pageable operands bounce; pinned ones are used through their mapping
-        rc = bounced(win == Where::Pageable ? inbuf : pin,
-                     wio == Where::Pageable ? inoutbuf : (void *) pio, (uint64_t) count, it, ext,
-                     (uint32_t) op, win == Where::Pageable, wio == Where::Pageable, dev);
+    const mpix::HostCall call{win, wio,
+                              win == Where::Device && wio == Where::Device && din != dio &&
+                                  peer_state(dio, din) == kPeerNone,
+                              (uint64_t) count * ext, opi == kOpEqual,
+                              g_zero_copy.load(), g_bounce_bytes, g_pipe_threads.load(),
+                              g_pipe_wave.load() != 0, g_pipe_chunk.load()};
+    const int peer = call.no_peer ? din : -1;   // `in`'s device, copied from with PeerAsync
+    // a form that cannot have its buffers answers -1: the next one, then
+    for (mpix::Route declined = mpix::Route::None;;) {
+        const mpix::HostRoute r = mpix::host_route(call, declined);
+        // an operand the form copies itself as the caller gave it, another
+        // as the device sees it
+        const Combine c{r.in_host ? inbuf : pin, r.io_host ? inoutbuf : (void *) pio,
+                        (uint64_t) count, it, ext, (uint32_t) op};
+        // the wave and worker forms have streams of their own, the others
+        // use the calling thread's
+        const bool pipes = r.route == mpix::Route::Wave || r.route == mpix::Route::Worker;
+        DevState *d = pipes ? nullptr : dev_state(dev);
+        if (!pipes && !d)
+            return set_err(MPIX_REDOP_ERR_OTHER);
+        switch (r.route) {
+            case mpix::Route::PeerStaged:
+            case mpix::Route::Staged: rc = staged(d, c, r.in_host, r.io_host, dev, peer); break;
+            case mpix::Route::PeerEqual:
+            case mpix::Route::EqualWhole:
+                rc = equal_whole(d, c, r.in_host, r.io_host, dev, peer);
+                break;
+            case mpix::Route::Bounce: rc = bounced(d, c, r.in_host, r.io_host); break;
+            case mpix::Route::Wave: rc = waved(c, r.in_host, r.io_host, dev, call.threads); break;
+            case mpix::Route::Worker:
+                rc = pipelined(c, r.in_host, r.io_host, dev, call.threads);
+                break;
+            default: rc = run_sync(d, c, r.zero_copy);
+        }
         if (rc >= 0)
             return set_err(rc);
+        declined = r.route;
     }
-    if (opi == kOpEqual && (in_stage || io_stage))
-        // MPIX_EQUAL is one comparison over the whole buffer behind one
-        // 8-byte header (opequal.c:20-35; MPIR_Reduce_equal: "we can't split
-        // the message"), so it is never chunked
-        return set_err(equal_whole(in_stage ? inbuf : pin, io_stage ? inoutbuf : (void *) pio,
-                                   (uint64_t) count, in_stage, io_stage, dev));
-    const int pipe_threads = g_pipe_threads.load();
-    const bool wave = g_pipe_wave.load() != 0;
-    if (pageable && zc && pipe_threads > 0 &&
-        (uint64_t) count * ext >= (wave ? 2 : 2 * (uint64_t) pipe_threads) * g_pipe_chunk.load()) {
-        // pageable operands through the workers' pinned slots; a pinned
-        // operand is used through its device mapping
-        rc = (wave ? waved : pipelined)(win == Where::Pageable ? inbuf : pin,
-                                        wio == Where::Pageable ? inoutbuf : (void *) pio,
-                                        (uint64_t) count, it, ext, (uint32_t) op,
-                                        win == Where::Pageable, wio == Where::Pageable, dev,
-                                        pipe_threads);
-        if (rc >= 0)
-            return set_err(rc);
-    }
-    if (in_stage || io_stage)
-        return set_err(staged(in_stage ? inbuf : pin, io_stage ? inoutbuf : (void *) pio,
-                              (uint64_t) count, it, ext, (uint32_t) op, in_stage, io_stage, dev));
-    DevState *d = dev_state(dev);
-    if (!d)
-        return set_err(MPIX_REDOP_ERR_OTHER);
-    return set_err(run_sync(d, pin, (void *) pio, (uint64_t) count, it, ext, (uint32_t) op,
-                            win == Where::Pinned || wio == Where::Pinned));
 }
 
 int MPIX_Reduce_local_vector_async(const void *inbuf, void *inoutbuf, MPIX_Aint count,
@@ -2923,8 +2688,7 @@ static int plan_enqueue(const void *origin, void *result, void *target, MPIX_Iov
     if (p->nrun == 1) {
         char *t1 = (char *) q.target + p->one_off;
         if (!fetch)
-            return enqueue(po, t1, p->total, p->it, p->ext, op, s, nullptr, nullptr, 0, nullptr,
-                           q.zc);
+            return enqueue(Combine{po, t1, p->total, p->it, p->ext, op}, s, q.zc);
         return getacc_launch(po, pr, t1, p->total, 1, 1, p->it, p->ext, opi, q.zc, s);
     }
     const mpix::PlanEntry *en = opi < kOpReplace ? plan_entry(opi, p->it) : nullptr;

@@ -1014,6 +1014,60 @@ def test_pageable_worker_modes(db, aff, mode):
     assert p.returncode == 0 and 'mode ok' in p.stdout, p.stdout + p.stderr
 
 
+_HOST_FORMS_FINALIZE = r'''
+import sys, numpy as np, torch
+sys.path.insert(0, %r)
+from mpich_amd import redop as R, handles as H
+from oracle import oracle as orc
+orc.build()
+EQUAL = 0x5800000f
+rng = np.random.default_rng(11)
+n = (1 << 18) + 5
+a = rng.uniform(-1, 1, n).astype(np.float32); b = rng.uniform(-1, 1, n).astype(np.float32)
+nb = (4 << 20) + 8
+x = rng.integers(0, 256, nb, dtype=np.uint8); x[:8] = np.array([1], '<u8').view(np.uint8)
+y = x.copy(); y[nb - 3] ^= 0x10
+torch.zeros(1).cuda()
+
+def check(inbuf, inout, count, dt, op, what):
+    exp = inout.copy()
+    assert orc.reduce_local(inbuf.copy(), exp, count, dt, op) == 0
+    got = inout.copy()
+    assert R.MPI_Reduce_local(inbuf, got, count, dt, op) == 0, what
+    assert np.array_equal(got.view(np.uint8), exp.view(np.uint8)), what
+
+for rep in range(2):
+    assert R.set_pageable(4, 64 << 10) == 0
+    check(b, a, 1000, H.MPI_FLOAT, H.MPI_SUM, ('bounce', rep))
+    check(b, a, n, H.MPI_FLOAT, H.MPI_SUM, ('wave or worker', rep))
+    assert R.set_pageable(0, 64 << 10) == 0
+    check(b, a, n, H.MPI_FLOAT, H.MPI_SUM, ('staged', rep))
+    check(x, x.copy(), nb, H.MPI_BYTE, EQUAL, ('equal', rep))
+    check(y, x, nb, H.MPI_BYTE, EQUAL, ('not equal', rep))
+    assert R.finalize() == 0
+print('forms ok')
+'''
+
+
+@pytest.mark.parametrize('mode,trace', [('wave', 'wave_trace'), ('worker', 'pipe_trace')])
+def test_host_forms_across_finalize(mode, trace):
+    """MPIX_Redop_finalize frees the bounce buffer, the workers' slots, the
+    wave's ring and the device scratch: in a fresh process the bounce, wave
+    (or worker), staged and whole-buffer MPIX_EQUAL forms once each, pageable
+    operands, then finalize, then all of them again on new buffers; every
+    result bit-equal to the oracle, and the step trace shows the wave (worker)
+    form ran both times"""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    p = subprocess.run([sys.executable, '-c', _HOST_FORMS_FINALIZE % root], capture_output=True,
+                       text=True, timeout=300,
+                       env=dict(os.environ, MPIX_REDOP_PAGEABLE_MODE=mode,
+                                MPIX_REDOP_PIPE_TRACE='1'))
+    assert p.returncode == 0 and 'forms ok' in p.stdout, p.stdout + p.stderr[-4000:]
+    assert p.stderr.count('{"%s"' % trace) == 2, p.stderr[-2000:]
+
+
 def test_pageable_knob_errors(R):
     prev = R.get_pageable()
     assert R.set_pageable(-1, 1 << 20) == 12

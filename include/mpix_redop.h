@@ -168,7 +168,22 @@ int MPIX_Redop_finalize(void);
  *
  * MPIX_Reduce_local_async: both buffers must be device-accessible; the
  * kernel is enqueued on `stream` (a hipStream_t, NULL = legacy default
- * stream) and the call returns without waiting. */
+ * stream) and the call returns without waiting.
+ *
+ * Threads: any number of threads may call any entry at once, and any number
+ * may enqueue on one stream -- a user stream, the null stream, or
+ * hipStreamPerThread (a stream of its own in every thread) -- with the same
+ * results as the calls one after another in the stream's order.  The kernels
+ * keep no state between launches, with one exception the library serialises
+ * itself: MPI_PROD on MPI_COMPLEX32 and MPI_C_LONG_DOUBLE_COMPLEX runs as two
+ * launches that share a per-stream device buffer (per stream and thread for
+ * hipStreamPerThread); each such call holds that buffer's lock over both
+ * enqueues, so no other thread's pair comes between them, and records an event
+ * behind them, without which the buffer is never freed or replaced.
+ * MPIX_Redop_finalize from one thread leaves other threads' calls alone, in
+ * flight or enqueued: it frees buffers that are idle, waits for the events (not
+ * the streams) behind buffers with work still queued, and leaves a buffer a caller holds
+ * to that caller; the next such call on a stream makes a buffer again. */
 int MPIX_Reduce_local(const void *inbuf, void *inoutbuf, MPIX_Aint count,
                       MPIX_Datatype datatype, MPIX_Op op);
 int MPIX_Reduce_local_async(const void *inbuf, void *inoutbuf, MPIX_Aint count,
@@ -360,9 +375,10 @@ int MPIX_Get_accumulate_local_iovec_async(const void *origin, void *result, void
  * One exception: a plan of exactly one run takes the contiguous entries' path
  * (below), and with it their one piece of shared state.  In the reduce form the
  * split combiners (the x87 and binary128 types' ops) use the per-(device,
- * stream) fixup buffer of MPIX_Reduce_local_async: its first use on a stream,
- * and a later call that needs a larger one, take a global mutex and may
- * allocate or synchronise that stream.  So for such a plan, type and op, run one
+ * stream) fixup buffer of MPIX_Reduce_local_async: every such call takes the
+ * buffer's lock around its two launches and records an event after them, and
+ * its first use on a stream, and a later call that needs a larger one,
+ * allocate.  So for such a plan, type and op, run one
  * call of at least that size on the stream before capturing or relying on a
  * call not to block -- exactly what MPIX_Reduce_local_async itself asks for.
  * Every other single-run call, the fetch form included, holds to the rule.

@@ -28,6 +28,7 @@
 
 #include "mpix_redop.h"
 #include "redop_dispatch.h"
+#include "redop_fixup.h"
 #include "redop_hostpath.h"
 
 using mpix::Entry;
@@ -1375,29 +1376,75 @@ struct DeviceGuard {
 };
 
 // ------------------------------------------- split combiners' fixup words
-// One buffer per (device, stream) for the words k_contig32 writes for a split
-// combiner (redop_kernels.h is_split): stream order serialises its users on
-// one stream, and no two streams share one.
-struct FixupBuf {
-    int dev;
-    uintptr_t stream;
-    void *ptr;
-    size_t bytes;
-};
-std::mutex g_fixup_mu;
-std::vector<FixupBuf> g_fixup;
-
-void free_fixup_buffers()
-{
-    std::lock_guard<std::mutex> l(g_fixup_mu);
-    for (FixupBuf &f : g_fixup) {
-        DeviceGuard g(f.dev);
-        (void) hipStreamSynchronize((hipStream_t) f.stream);
-        (void) hipFree(f.ptr);
+// The words k_contig32 writes and k_fixup32 reads for a split combiner
+// (redop_kernels.h is_split) live in buffers kept by redop_fixup.h's registry,
+// which states the rules (one holder per key from acquire to release, a free
+// only behind a completed event, at most kFixupMaxIdle idle buffers); these
+// are its HIP operations.
+struct FixupHipOps {
+    void *alloc(int dev, size_t bytes)
+    {
+        DeviceGuard g(dev);
+        void *p = nullptr;
+        if (hipMalloc(&p, bytes) != hipSuccess) {
+            (void) hipGetLastError();
+            return nullptr;
+        }
+        return p;
     }
-    g_fixup.clear();
-    (void) hipGetLastError();
-}
+    void free(int dev, void *p)
+    {
+        DeviceGuard g(dev);
+        (void) hipFree(p);
+        (void) hipGetLastError();
+    }
+    void *record(int dev, uintptr_t stream, void *ev)
+    {
+        DeviceGuard g(dev);
+        hipEvent_t e = (hipEvent_t) ev;
+        // the event says only that the kernels before it are through with the
+        // words (nobody reads results behind it): no timing, and no cache
+        // write-back and invalidation between one call's kernels and the next's
+        if (!e && hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventDisableSystemFence) !=
+                      hipSuccess) {
+            (void) hipGetLastError();
+            return nullptr;
+        }
+        if (hipEventRecord(e, (hipStream_t) stream) != hipSuccess) {
+            (void) hipGetLastError();
+            if (!ev)
+                (void) hipEventDestroy(e);
+            return nullptr;
+        }
+        return e;
+    }
+    bool done(void *ev)
+    {
+        const hipError_t e = hipEventQuery((hipEvent_t) ev);
+        if (e != hipSuccess)
+            (void) hipGetLastError();
+        return e == hipSuccess;
+    }
+    bool wait(void *ev)
+    {
+        const hipError_t e = hipEventSynchronize((hipEvent_t) ev);
+        if (e != hipSuccess)
+            (void) hipGetLastError();
+        return e == hipSuccess;
+    }
+    void drop(int dev, void *ev)
+    {
+        DeviceGuard g(dev);
+        (void) hipEventDestroy((hipEvent_t) ev);
+    }
+    bool sync(int dev, uintptr_t stream)
+    {
+        DeviceGuard g(dev);
+        return hipStreamSynchronize((hipStream_t) stream) == hipSuccess;
+    }
+};
+using FixupReg = mpix::FixupRegistry<FixupHipOps>;
+FixupReg *g_fixup = new FixupReg(FixupHipOps{});    // never destroyed (no HIP call at exit)
 
 // ------------------------------------------- peer access between devices
 // A kernel on device `dev` may dereference another device's hipMalloc memory
@@ -1773,38 +1820,22 @@ mpix::CopyMode copy_mode(uint32_t opi, bool fetch)
 }  // namespace
 
 namespace mpix {
-uint64_t *fixup_buffer(hipStream_t s, size_t bytes)
+FixupLease fixup_acquire(hipStream_t s, size_t bytes)
 {
     int dev = 0;
-    if (hipStreamGetDevice(s, &dev) != hipSuccess)
-        return nullptr;
-    std::lock_guard<std::mutex> l(g_fixup_mu);
-    FixupBuf *f = nullptr;
-    for (FixupBuf &e : g_fixup)
-        if (e.dev == dev && e.stream == (uintptr_t) s)
-            f = &e;
-    if (!f) {
-        g_fixup.push_back(FixupBuf{dev, (uintptr_t) s, nullptr, 0});
-        f = &g_fixup.back();
+    if (hipStreamGetDevice(s, &dev) != hipSuccess) {
+        (void) hipGetLastError();
+        return FixupLease{};
     }
-    if (f->bytes < bytes) {
-        DeviceGuard g(dev);
-        if (f->ptr) {       // enqueued work on this stream may still read the old one
-            if (hipStreamSynchronize(s) != hipSuccess)
-                return nullptr;
-            (void) hipFree(f->ptr);
-            f->ptr = nullptr;
-            f->bytes = 0;
-        }
-        size_t want = bytes < ((size_t) 64 << 10) ? (size_t) 64 << 10 : bytes;
-        if (hipMalloc(&f->ptr, want) != hipSuccess) {
-            (void) hipGetLastError();
-            f->ptr = nullptr;
-            return nullptr;
-        }
-        f->bytes = want;
-    }
-    return static_cast<uint64_t *>(f->ptr);
+    // hipStreamPerThread is one handle value and a stream of its own in every thread
+    const FixupKey key{dev, (uintptr_t) s, s == hipStreamPerThread ? fixup_thread_token() : 0};
+    const FixupReg::Lease l = g_fixup->acquire(key, bytes);
+    return FixupLease{static_cast<uint64_t *>(l.ptr), l.entry};
+}
+
+void fixup_release(const FixupLease &lease)
+{
+    g_fixup->release(FixupReg::Lease{lease.words, lease.entry});
 }
 }  // namespace mpix
 
@@ -1857,7 +1888,7 @@ static void free_states(DevState *arr)
 
 int MPIX_Redop_finalize(void)
 {
-    free_fixup_buffers();
+    g_fixup->finalize();
     std::vector<DevState *> pooled;
     {
         std::lock_guard<std::mutex> l(g_pool_mu);
@@ -3042,9 +3073,15 @@ int MPIX_Reduce_local_tree_async(const void *const *inbufs, int ninputs, void *o
         return set_err(MPIX_REDOP_ERR_ARG);
     uint32_t it;
     uint64_t ext;
-    // outbuf may be one of the slots itself (each lane reads all its slots'
-    // elements before it writes that element); any partial overlap is
-    // refused.  Slots 1..k-1 may be NULL: absent (the partner passes through).
+    // outbuf may be one of the slots itself; any partial overlap is refused.
+    // What makes that safe: the tree kernels read all their slots' elements
+    // of a unit before they write that unit, and a unit is one lane's alone.
+    // The two-launch split combiners on the 32-byte route do not (k_contig32
+    // stores the inout role's value into a unit it declines and k_fixup32
+    // reads both operands again): there out over slot 0 is safe because slot 0
+    // is that role, and out over slot 1 goes to the element kernel
+    // (launch_tree).  Slots 1..k-1 may be NULL: absent (the partner passes
+    // through).
     for (int q = 0; q < ninputs; ++q) {
         if (!inbufs[q])
             continue;

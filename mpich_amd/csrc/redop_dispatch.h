@@ -29,7 +29,7 @@ struct Params {
     uint32_t wt_phase = 0;
     uint32_t wt_xcd = 0;        // and every block running on an XCD whose bit is set
     // split combiners (is_split, redop_kernels.h): one 64-bit word per 64
-    // units, bit j set when unit 64 w + j left its fast path (fixup_buffer)
+    // units, bit j set when unit 64 w + j left its fast path (fixup_acquire)
     uint64_t *fixup = nullptr;
 };
 
@@ -219,13 +219,20 @@ hipError_t launch_cas_atomic(uint32_t size, const void *origin, const void *comp
 // MPIX_EQUAL on an MPI_BYTE buffer of n >= 8 bytes (opequal.c:20-35)
 hipError_t launch_equal(const void *in, void *io, uint64_t n, hipStream_t s);
 
-// up to kMaxMultiInputs independent device copies in one launch
 // A device buffer of at least `bytes` for the split combiners' fixup words,
-// one per (device, stream): stream order serialises its users; grown (after
-// synchronising the stream) when a larger call comes; freed by
-// MPIX_Redop_finalize.  nullptr when it cannot be allocated.
-uint64_t *fixup_buffer(hipStream_t s, size_t bytes);
+// the caller's from fixup_acquire until fixup_release: it enqueues k_contig32
+// and k_fixup32 on `s` in between, and no other caller's pair comes between
+// them on that stream (one buffer per device and stream, per calling thread
+// for hipStreamPerThread; redop_fixup.h has the lifetime rules).  words is
+// nullptr when none can be had: nothing to release then.
+struct FixupLease {
+    uint64_t *words = nullptr;
+    void *entry = nullptr;
+};
+FixupLease fixup_acquire(hipStream_t s, size_t bytes);
+void fixup_release(const FixupLease &lease);
 
+// up to kMaxMultiInputs independent device copies in one launch
 hipError_t launch_copy_multi(const void *const *srcs, void *const *dsts, const uint64_t *bytes,
                              int n, hipStream_t s, unsigned wt_xcd = 0);
 

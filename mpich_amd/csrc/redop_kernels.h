@@ -1075,10 +1075,15 @@ hipError_t launch_contig32(const typename C::unit *in, const typename C::unit *i
     Params p = prm;
     p.done = nullptr;
     set_store_policy(p, cfg, grid);
+    // a split combiner holds its stream's word buffer over both launches: no
+    // other caller's pair comes between them on `s`, and the buffer is not
+    // freed under them
+    FixupLease lease;
     if constexpr (is_split<C>::value) {
-        p.fixup = fixup_buffer(s, (count + 63) / 64 * sizeof(uint64_t));
-        if (!p.fixup)
+        lease = fixup_acquire(s, (count + 63) / 64 * sizeof(uint64_t));
+        if (!lease.words)
             return hipErrorOutOfMemory;
+        p.fixup = lease.words;
     }
     hipLaunchKernelGGL((k_contig32<C, U32, MPIX_REDOP_NT_LOAD, MPIX_REDOP_NT_STORE>), dim3(grid),
                        dim3(kContig32Block), 0, s, in, io, out, count, p, grid, kContig32Block);
@@ -1087,7 +1092,10 @@ hipError_t launch_contig32(const typename C::unit *in, const typename C::unit *i
         const unsigned g2 = grid_for(256, (count + 63) / 64, 0, 256);
         hipLaunchKernelGGL((k_fixup32<C>), dim3(g2), dim3(256), 0, s, in, io, out, count, p, g2);
     }
-    return hipGetLastError();
+    const hipError_t e = hipGetLastError();
+    if constexpr (is_split<C>::value)
+        fixup_release(lease);
+    return e;
 }
 
 // Contiguous launcher: chooses the packet or the element-wise kernel.
@@ -1233,8 +1241,13 @@ hipError_t launch_tree(const void *const *ins, int k, void *out, uint64_t count,
     if constexpr (sizeof(T) > 16) {
         // out = slot 0 OP slot 1 on 32-byte units, all three 16-byte aligned:
         // k_contig32 with slot 0 in the inout role (recursive halving's
-        // combine_to); other shapes go element-wise below
-        if (k == 2 && pres == 3u &&
+        // combine_to); other shapes go element-wise below.  So does a split
+        // combiner whose output is slot 1: k_contig32 stores the inout role's
+        // value (slot 0's) into every unit it declines, and k_fixup32 would
+        // then read that where it expects slot 1's (out over slot 0 stores
+        // slot 0's value over itself)
+        const bool over_in = is_split<C>::value && out == ins[1];
+        if (k == 2 && pres == 3u && !over_in &&
             ((ao | reinterpret_cast<uintptr_t>(ins[0]) | reinterpret_cast<uintptr_t>(ins[1])) & 15) ==
                 0) {
             return launch_contig32<C>(mi.p[1], mi.p[0], tout, count, prm, cfg, s);

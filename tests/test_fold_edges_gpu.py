@@ -19,7 +19,10 @@ Kernels by launch condition (launch_multi / launch_tree): operands of a unit
 of at most 16 bytes that share the output's 16-byte phase run the packet
 kernels (k_contig_multi; k_contig_tree_rec<2,2> at k = 2, k_contig_tree<4,2>
 at 4, k_contig_tree_rec<8,1> at 8, <16,1> at 16), any other placement and
-every 32-byte unit the element kernels (k_elem_multi, k_elem_tree)."""
+every 32-byte unit the element kernels (k_elem_multi, k_elem_tree) -- but for
+the two-slot tree of 32-byte units with both slots present and all three
+operands on the 16-byte grid, which runs k_contig32 (tests/test_soft_fp_gpu.py
+test_two_slot_tree_output_placement)."""
 import types
 
 import numpy as np
@@ -36,7 +39,9 @@ KINDS = {(s[0], s[1]): (s[2], s[3]) for s in SWEEP}
 KINDS.update({('MPI_FLOAT', 'MPI_REPLACE'): ('fp', 4), ('MPI_FLOAT', 'MPI_NO_OP'): ('fp', 4),
               # 32-byte units: bit for bit against the oracle
               ('MPI_LONG_DOUBLE_INT', 'MPI_MAXLOC'): ('int', 32),
-              ('MPI_COMPLEX32', 'MPI_PROD'): ('int', 32)})
+              ('MPI_COMPLEX32', 'MPI_PROD'): ('int', 32),
+              ('MPI_COMPLEX32', 'MPI_SUM'): ('int', 32),
+              ('MPI_C_LONG_DOUBLE_COMPLEX', 'MPI_PROD'): ('int', 32)})
 
 
 @pytest.fixture(scope='module')
@@ -422,7 +427,7 @@ def test_tree_count_edges(R, H, oracle, dtname, opname, k):
                     check_tree(R, oracle, t, n, vals, Sn, pres, off, in_place, (off,))
 
 
-@pytest.mark.parametrize('k', [4, 8])
+@pytest.mark.parametrize('k', [2, 4, 8])
 @pytest.mark.parametrize('dtname,opname,zero_im', [('MPI_LONG_DOUBLE_INT', 'MPI_MAXLOC', False),
                                                    ('MPI_COMPLEX32', 'MPI_PROD', False),
                                                    ('MPI_COMPLEX32', 'MPI_PROD', True)],
@@ -430,7 +435,10 @@ def test_tree_count_edges(R, H, oracle, dtname, opname, k):
 def test_tree_wide_units(R, H, oracle, dtname, opname, zero_im, k):
     """B3: 32-byte units run k_elem_tree's tree_fold_rec<0, 16> branch at every
     k above 2: x87 specials under MAXLOC, the binary128 complex product on its
-    fast path and (zero imaginary parts) on the general one"""
+    fast path and (zero imaginary parts) on the general one.  At k = 2 with
+    both slots present and everything on the 16-byte grid they run k_contig32
+    (the product its two launches; over slot 1 k_elem_tree, launch_tree).
+    Output: separate, over slot 0, over slot 1 and over the last present slot"""
     t = ty(R, H, dtname, opname)
     rng = np.random.default_rng(seed(dtname, zero_im, k, 'B3'))
     masks = [(1 << k) - 1, 1, SPARSE[k], M.odd_upper_absent(k) & ~2]
@@ -439,6 +447,8 @@ def test_tree_wide_units(R, H, oracle, dtname, opname, zero_im, k):
                 for x in _soft_operands(H, rng, dtname, n, zero_im)]
         for offs, out_off in (([0] * k, 0), ([16 * (q % 2) for q in range(k)], 16)):
             S = [place(x, o) for x, o in zip(vals, offs)]
-            for pres in masks:
-                for in_place in (None, 0):
+            for pres in dict.fromkeys(masks):
+                last = pres.bit_length() - 1
+                outs = [None, 0] + sorted({q for q in (1, last) if q and (pres >> q) & 1})
+                for in_place in outs:
                     check_tree(R, oracle, t, n, vals, S, pres, out_off, in_place, (offs[1],))

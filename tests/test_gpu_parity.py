@@ -701,8 +701,9 @@ def test_tree_combine(R, H, oracle, k, dtname, opname):
 
 def test_concurrent_callers(R, H, oracle):
     """MPIR_Reduce_local is reentrant (called with the global CS held by
-    different threads under MPI_THREAD_MULTIPLE): per-thread streams, no
-    shared state on the data path."""
+    different threads under MPI_THREAD_MULTIPLE): per-thread streams, and no
+    shared state on this data path (the two-launch complex products share a
+    word buffer: tests/test_split_concurrent_gpu.py restates this test for them)."""
     import threading
     n = (1 << 20) + 11
     rng = np.random.default_rng(99)

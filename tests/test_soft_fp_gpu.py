@@ -223,6 +223,109 @@ def test_split_fixup_buffer_grows_on_a_stream(R, oracle):
         _same(da.cpu().numpy(), want, n, ('grow', n))
 
 
+def test_split_fixup_buffer_grows_under_queued_work(R, H, oracle):
+    """the larger call is enqueued while the small call's kernels are still
+    queued behind a 64 MiB fp32 combine on the same stream: the small
+    buffer, which those kernels name, may go only once they are through
+    (the registry retires it behind an event; redop_fixup.h)"""
+    rng = np.random.default_rng(0x5EED0960)
+    s = torch.cuda.Stream()
+    dt = S.COMPLEX32
+    nf = 16 << 20
+    fa, fb = rng.uniform(-1, 1, nf).astype(np.float32), rng.uniform(-1, 1, nf).astype(np.float32)
+    jobs = []
+    for n in (1000, (1 << 20) + 17):
+        a, b = _split_operands(rng, dt, n, [0, 63, 64, n - 1] + rng.integers(0, n, 16).tolist())
+        jobs.append((n, dev(a), dev(b), _oracle_prod(oracle, dt, a, b)))
+    dfa, dfb = dev(fa), dev(fb)
+    assert R.reduce_local_async(dfb, dfa, nf, H.MPI_FLOAT, H.MPI_SUM, s) == 0
+    for n, da, db, _ in jobs:
+        assert R.reduce_local_async(db, da, n, dt, S.MPI_PROD, s) == 0
+    s.synchronize()
+    for n, da, _, want in jobs:
+        _same(da.cpu().numpy(), want, n, ('grow queued', n))
+    assert np.array_equal(dfa.cpu().numpy().view(np.float32), fa + fb)
+
+
+@pytest.fixture(scope='module')
+def H():
+    from mpich_amd import handles
+    return handles
+
+
+# The two-slot tree on the 32-byte route with its output on either slot.  The
+# split combiners are two launches: k_contig32 stores the inout role's value
+# (slot 0's) into every unit it declines and k_fixup32 reads both operands
+# again, so with out == slot 1 the pair would compute slot 0 . slot 0 in every
+# declined unit; launch_tree sends that placement to k_elem_tree.  The
+# non-split combiners of the same launcher (COMPLEX32 SUM, LONG_DOUBLE_INT
+# MAXLOC) read before they write and take all three placements.
+TREE2 = [('MPI_COMPLEX32', 'MPI_PROD', False), ('MPI_COMPLEX32', 'MPI_PROD', True),
+         ('MPI_C_LONG_DOUBLE_COMPLEX', 'MPI_PROD', False),
+         ('MPI_C_LONG_DOUBLE_COMPLEX', 'MPI_PROD', True),
+         ('MPI_COMPLEX32', 'MPI_SUM', False), ('MPI_LONG_DOUBLE_INT', 'MPI_MAXLOC', False)]
+TREE2_COUNTS = (1, 63, 64, 65, 128, 4099)   # k_contig32's tile: 64 units
+
+
+@pytest.mark.parametrize('dtname,opname,zero_im', TREE2,
+                         ids=['%s-%s%s' % (d[4:], o[4:], '-real' if z else '') for d, o, z in TREE2])
+def test_two_slot_tree_output_placement(R, H, oracle, dtname, opname, zero_im):
+    """out = slot 0 OP slot 1 into a separate output, over slot 0 and over
+    slot 1; a partial tile, a full one, a full and a partial one, many; all
+    three operands on the 16-byte grid (k_contig32 and, for the products,
+    k_fixup32) and with slot 1 on a +16 and a separate output on a +8 byte
+    offset (k_elem_tree); declined units at 0, 63, 64, n - 1 and at random
+    positions, or everywhere (zero imaginary parts).  check_tree asserts
+    return code 0, the other slot(s) unchanged, the guard bytes, the bits of
+    the single-call sequence and the oracle's (all 32 bytes of every unit; the
+    pair's over its type map)."""
+    from tests import test_fold_edges_gpu as F
+    from tests.test_getacc_gpu import _soft_operands
+    t = F.ty(R, H, dtname, opname)
+    assert t.ext == 32
+    rng = np.random.default_rng(F.seed(dtname, opname, zero_im, 'tree2'))
+    for n in TREE2_COUNTS:
+        if 'COMPLEX' in dtname:
+            dt = S.C_LD_COMPLEX if 'LONG_DOUBLE' in dtname else S.COMPLEX32
+            at = {0, 63, 64, n - 1} | set(rng.integers(0, n, 1 + n // 100).tolist())
+            a, b = _split_operands(rng, dt, n, sorted(u for u in at if u < n))
+            if zero_im:
+                a[:, 16:] = 0
+                b[:, 16:] = 0
+        else:
+            a, b = _soft_operands(H, rng, dtname, n, False)
+        vals = [a.reshape(-1), b.reshape(-1)]
+        for offs, out_off in (([0, 0], 0), ([0, 16], 8)):
+            slots = [F.place(x, o) for x, o in zip(vals, offs)]
+            for in_place in (None, 0, 1):
+                F.check_tree(R, oracle, t, n, vals, slots, 3, out_off, in_place, (offs[1],))
+
+
+@pytest.mark.parametrize('dt', [S.COMPLEX32, S.C_LD_COMPLEX], ids=['complex32', 'c_long_double'])
+def test_split_batch_two_pairs_one_buffer(R, oracle, dt):
+    """the batch entry with two split triples: two kernel pairs follow each
+    other on one word buffer within one call, the second pair's words written
+    over the first's.  Counts 5 and 4099 in both orders; the small triple with
+    every unit declined against the large one's few, and the reverse."""
+    rng = np.random.default_rng(0x5EED0950 + dt)
+    s = torch.cuda.current_stream()
+    for small_real in (True, False):
+        a5, b5 = _split_operands(rng, dt, 5, [] if small_real else [3])
+        aL, bL = _split_operands(rng, dt, 4099, [0, 1, 4, 63, 64, 4098] if small_real else [])
+        for x in ((a5, b5) if small_real else (aL, bL)):
+            x[:, 16:] = 0
+        want5, wantL = _oracle_prod(oracle, dt, a5, b5), _oracle_prod(oracle, dt, aL, bL)
+        for order in ((0, 1), (1, 0)):
+            trip = [(dev(a5), dev(b5), 5, want5, a5, b5), (dev(aL), dev(bL), 4099, wantL, aL, bL)]
+            trip = [trip[i] for i in order]
+            assert R.reduce_local_batch_async([x[1] for x in trip], [x[0] for x in trip],
+                                              [x[2] for x in trip], dt, S.MPI_PROD, s) == 0
+            s.synchronize()
+            for da, db, n, want, _, b in trip:
+                _same(da.cpu().numpy(), want, n, ('batch', small_real, order, n))
+                assert np.array_equal(db.cpu().numpy(), b.reshape(-1).view(np.uint8)), ('in', n)
+
+
 @pytest.mark.parametrize('dt', [S.COMPLEX32, S.C_LD_COMPLEX], ids=['complex32', 'c_long_double'])
 def test_split_product_every_unit_declined(R, oracle, dt):
     """real values stored as complex: every product has a zero operand, so

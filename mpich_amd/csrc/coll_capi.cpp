@@ -37,7 +37,10 @@
 #include <utility>
 #include <vector>
 
+#include "coll_sched.h"
 #include "mpix_coll.h"
+
+using namespace coll_sched;
 
 namespace {
 
@@ -155,16 +158,6 @@ void ran_instead(MPIX_Comm c, int *last, int alg)
 
 #define TRY(x) do { int rc_ = (x); if (rc_ != MPIX_REDOP_SUCCESS) return rc_; } while (0)
 #define HTRY(x) do { if ((x) != hipSuccess) return MPIX_REDOP_ERR_OTHER; } while (0)
-
-size_t round256(size_t b) { return (b + 255) & ~(size_t) 255; }
-
-int pof2_of(int n)
-{
-    int p = 1;
-    while (p * 2 <= n)
-        p *= 2;
-    return p;
-}
 
 int set_device(MPIX_Comm c)
 {
@@ -531,6 +524,9 @@ int combine_multi(MPIX_Comm c, const std::vector<const void *> &ins, void *inout
     return MPIX_REDOP_SUCCESS;
 }
 
+// out = a OP b (a in the inout role, b in the in role) without first copying
+// a into out: one 2-slot tree kernel (MPIX_Reduce_local_tree_async); host /
+// custom-combine communicators copy, then combine -- the same operands either way
 int combine_to(MPIX_Comm c, const void *a, const void *b, void *out, MPIX_Aint count,
                MPIX_Datatype dt, MPIX_Op op, hipStream_t s, size_t ext)
 {
@@ -543,12 +539,6 @@ int combine_to(MPIX_Comm c, const void *a, const void *b, void *out, MPIX_Aint c
     TRY(copy(c, out, a, (size_t) count * ext, s));
     return combine(c, b, out, count, dt, op, s);
 }
-
-// out = a OP b (a in the inout role, b in the in role) without first copying
-// a into out: one 2-slot tree kernel (MPIX_Reduce_local_tree_async); host /
-// custom-combine communicators copy, then combine -- the same operands either way
-int combine_to(MPIX_Comm c, const void *a, const void *b, void *out, MPIX_Aint count,
-               MPIX_Datatype dt, MPIX_Op op, hipStream_t s, size_t ext);
 
 // The communicator's scratch is shared by every collective issued on it, on
 // any stream: a new user is ordered behind the previous one on the device
@@ -728,15 +718,13 @@ int rs_recursive_halving_overlap(const char *sb, char *rb, size_t rc, MPIX_Datat
     TRY(ensure_aux(c, 2));
     hipEvent_t ev_in = c->pipe_ev[0], ev_kept = c->pipe_ev[1];
     TRY(mark(c, "start", s));
-    int mask = size >> 1, send_idx = 0, recv_idx = 0;
+    Window win{0, size};
     bool in_rb = false, kept_pending = false;
     char *rbuf = nullptr;       // where this step's partner half lands
-    while (mask > 0) {
+    for (int mask = size >> 1; mask > 0; mask >>= 1) {
         const int dst = rank ^ mask;
-        if (rank < dst)
-            send_idx = recv_idx + mask;
-        else
-            recv_idx = send_idx + mask;
+        const Step st = halve(&win, rank < dst);
+        const int send_idx = st.send_lo, recv_idx = st.recv_lo;
         const bool first = mask == size >> 1;
         const char *cur = first ? sb : tmp_results;
         if (first)
@@ -776,8 +764,6 @@ int rs_recursive_halving_overlap(const char *sb, char *rb, size_t rc, MPIX_Datat
             TRY(combine_to(c, own, rbuf, out, (MPIX_Aint) n, dt, op, s, ext));
             TRY(mark(c, "combine", s));
         }
-        send_idx = recv_idx;
-        mask >>= 1;
     }
     if (kept_pending)
         HTRY(hipStreamWaitEvent(s, ev_kept, 0));
@@ -785,148 +771,6 @@ int rs_recursive_halving_overlap(const char *sb, char *rb, size_t rc, MPIX_Datat
         TRY(copy(c, rb, tmp_results + (size_t) rank * blk, blk, s));         // :232-240
     TRY(mark(c, "epilogue", s));
     return MPIX_REDOP_SUCCESS;
-}
-
-// MPIR_Reduce_scatter_intra_recursive_halving
-// (reduce_scatter_intra_recursive_halving.c:38-260; the _block variant,
-// reduce_scatter_block_intra_recursive_halving.c:38-260, is the case of
-// equal counts).  cnts[i] = elements of rank i's result block.
-int rs_recursive_halving(const char *sb, char *rb, const std::vector<size_t> &cnts,
-                         MPIX_Datatype dt, MPIX_Op op, MPIX_Comm c, char *ws, hipStream_t s,
-                         size_t ext)
-{
-    const int rank = c->rank, size = c->size;
-    std::vector<size_t> disps(size, 0);
-    for (int i = 1; i < size; ++i)
-        disps[i] = disps[i - 1] + cnts[i - 1];
-    const size_t total = disps[size - 1] + cnts[size - 1];
-    if (!total)
-        return MPIX_REDOP_SUCCESS;
-    if (rh_overlap_applies(c, cnts, ext))
-        return rs_recursive_halving_overlap(sb, rb, cnts[0], dt, op, c, ws, s, ext);
-    char *tmp_results = ws;
-    char *tmp_recvbuf = ws + round256(total * ext);
-    const int pof2 = pof2_of(size), rem = size - pof2;
-    // P a power of two: no up-front copy of sendbuf into tmp_results (:91-96);
-    // the first step reads its halves from sendbuf and writes the combined
-    // half into tmp_results, the last writes this rank's block into recvbuf
-    // -- the same operands in the same roles, one HBM pass of the whole
-    // vector less
-    const bool direct = rem == 0;
-    TRY(mark(c, "start", s));
-    if (!direct) {
-        TRY(copy(c, tmp_results, sb, total * ext, s));                     // :91-96
-        TRY(mark(c, "local copy", s));
-    }
-    int newrank;
-    if (rank < 2 * rem) {                                                   // :110-137
-        if (rank % 2 == 0) {
-            TRY(exchange(c, {snd(rank + 1, tmp_results, total * ext)}, s));
-            newrank = -1;
-        } else {
-            TRY(exchange(c, {rcv(rank - 1, tmp_recvbuf, total * ext)}, s));
-            TRY(combine(c, tmp_recvbuf, tmp_results, (MPIX_Aint) total, dt, op, s));
-            newrank = rank / 2;
-        }
-        TRY(mark(c, "prologue", s));
-    } else {
-        newrank = rank - rem;
-    }
-    if (newrank != -1) {                                                    // :139-229
-        std::vector<size_t> newcnts(pof2), newdisps(pof2, 0);
-        for (int i = 0; i < pof2; ++i) {
-            int old_i = i < rem ? i * 2 + 1 : i + rem;
-            newcnts[i] = old_i < 2 * rem ? cnts[old_i] + cnts[old_i - 1] : cnts[old_i];
-        }
-        for (int i = 1; i < pof2; ++i)
-            newdisps[i] = newdisps[i - 1] + newcnts[i - 1];
-        auto sum = [&](int lo, int hi) {
-            size_t t = 0;
-            for (int i = lo; i < hi; ++i)
-                t += newcnts[i];
-            return t;
-        };
-        int mask = pof2 >> 1, send_idx = 0, recv_idx = 0, last_idx = pof2;
-        bool in_rb = false;         // this rank's block already written to recvbuf
-        while (mask > 0) {
-            int newdst = newrank ^ mask;
-            int dst = newdst < rem ? newdst * 2 + 1 : newdst + rem;
-            size_t send_cnt, recv_cnt;
-            if (newrank < newdst) {
-                send_idx = recv_idx + mask;
-                send_cnt = sum(send_idx, last_idx);
-                recv_cnt = sum(recv_idx, send_idx);
-            } else {
-                recv_idx = send_idx + mask;
-                send_cnt = sum(send_idx, recv_idx);
-                recv_cnt = sum(recv_idx, last_idx);
-            }
-            const char *cur = direct && mask == pof2 >> 1 ? sb : tmp_results;
-            // zero-length legs are skipped on both sides (:188-208)
-            TRY(exchange(c, {snd(dst, cur + newdisps[send_idx] * ext, send_cnt * ext),
-                             rcv(dst, tmp_recvbuf + newdisps[recv_idx] * ext, recv_cnt * ext)}, s));
-            TRY(mark(c, "exchange", s));
-            char *out = tmp_results + newdisps[recv_idx] * ext;
-            const char *own = cur + newdisps[recv_idx] * ext;
-            const size_t nbytes = recv_cnt * ext;
-            // the last step's half is this rank's block: written straight into
-            // recvbuf, unless that would overwrite the half being read -- with
-            // MPI_IN_PLACE at P = 2 the first step is the last and reads
-            // recvbuf itself ([disps[1], +c1) against [0, c1) at rank 1)
-            if (direct && mask == 1 && recv_idx == newrank &&
-                (own == rb || own + nbytes <= rb || rb + nbytes <= own)) {
-                out = rb;
-                in_rb = true;
-            }
-            TRY(combine_to(c, own, tmp_recvbuf + newdisps[recv_idx] * ext, out,
-                           (MPIX_Aint) recv_cnt, dt, op, s, ext));
-            TRY(mark(c, "combine", s));
-            send_idx = recv_idx;
-            last_idx = recv_idx + mask;
-            mask >>= 1;
-        }
-        if (!in_rb)
-            TRY(copy(c, rb, tmp_results + disps[rank] * ext, cnts[rank] * ext, s));   // :232-240
-    }
-    if (rank < 2 * rem) {                                                   // :245-262
-        if (rank % 2)
-            TRY(exchange(c, {snd(rank - 1, tmp_results + disps[rank - 1] * ext,
-                                 cnts[rank - 1] * ext)}, s));
-        else
-            TRY(exchange(c, {rcv(rank + 1, rb, cnts[rank] * ext)}, s));
-    }
-    TRY(mark(c, "epilogue", s));
-    return MPIX_REDOP_SUCCESS;
-}
-
-// True when the multipath recursive halving applies: P a power of two >= 4
-// and equal blocks (every rank's half has the same size at every step, so a
-// relay knows what it forwards without a size exchange).
-bool multipath_shape(const std::vector<size_t> &cnts, int size)
-{
-    if (size < 4 || (size & (size - 1)))
-        return false;
-    for (size_t n : cnts)
-        if (n != cnts[0])
-            return false;
-    return true;
-}
-
-// relay masks of a step with mask m: one of every pair {a, a ^ m}, a != m
-// (the smaller), so first hops (r ^ a) and second hops (r ^ a ^ m) together
-// use each of the other P - 2 links once
-std::vector<int> relay_masks(int m, int size)
-{
-    std::vector<int> A;
-    for (int a = 1; a < size; ++a)
-        if (a != m && a < (a ^ m))
-            A.push_back(a);
-    return A;
-}
-
-size_t multipath_relay_bytes(size_t recvcount, size_t ext, int size)
-{
-    return (size_t) (size / 2 - 1) * round256(recvcount * ext);
 }
 
 // One exchange step of a recursive-halving schedule routed over every link
@@ -945,36 +789,27 @@ int multipath_exchange(MPIX_Comm c, const char *sbase, char *rbase, size_t D, in
 {
     const int rank = c->rank;
     const std::vector<int> A = relay_masks(mask, c->size);
-    const size_t n = A.size() + 1;
-    auto lo = [&](size_t j) { return D * j / n; };   // part j: [lo(j), lo(j+1))
-    // chunks per part: >= 4 MiB each, at most 8 (one group when small)
-    size_t C = ((lo(1) - lo(0)) * ext) >> 22;
-    C = C < 1 ? 1 : (C > 8 ? 8 : C);
-    auto piece = [&](size_t j, size_t k, size_t *off, size_t *len) {
-        const size_t pl = lo(j + 1) - lo(j);
-        const size_t a = pl * k / C, b = pl * (k + 1) / C;
-        *off = lo(j) + a;
-        *len = b - a;
-    };
+    const PartCut cut(D, A.size() + 1, ext);
+    const size_t n = cut.n, C = cut.C;
     for (size_t g = 0; g <= C; ++g) {
         std::vector<MPIX_P2p_op> ops;
         size_t off, len;
         if (g < C) {
-            piece(0, g, &off, &len);
+            cut.piece(0, g, &off, &len);
             ops.push_back(snd(rank ^ mask, sbase + off * ext, len * ext));
             ops.push_back(rcv(rank ^ mask, rbase + off * ext, len * ext));
             for (size_t j = 1; j < n; ++j) {
-                piece(j, g, &off, &len);
+                cut.piece(j, g, &off, &len);
                 ops.push_back(snd(rank ^ A[j - 1], sbase + off * ext, len * ext));
-                ops.push_back(rcv(rank ^ A[j - 1], relay + (j - 1) * slot + (off - lo(j)) * ext,
-                                  len * ext));
+                ops.push_back(rcv(rank ^ A[j - 1],
+                                  relay + (j - 1) * slot + (off - cut.lo(j)) * ext, len * ext));
             }
         }
         if (g > 0) {
             for (size_t j = 1; j < n; ++j) {
-                piece(j, g - 1, &off, &len);
+                cut.piece(j, g - 1, &off, &len);
                 ops.push_back(snd(rank ^ A[j - 1] ^ mask,
-                                  relay + (j - 1) * slot + (off - lo(j)) * ext, len * ext));
+                                  relay + (j - 1) * slot + (off - cut.lo(j)) * ext, len * ext));
                 ops.push_back(rcv(rank ^ A[j - 1] ^ mask, rbase + off * ext, len * ext));
             }
         }
@@ -983,48 +818,123 @@ int multipath_exchange(MPIX_Comm c, const char *sbase, char *rbase, size_t D, in
     return MPIX_REDOP_SUCCESS;
 }
 
-// MPIX_RSB_RECURSIVE_HALVING_MULTIPATH: rs_recursive_halving's schedule with
-// every exchange step spread over all links (multipath_exchange), then one
-// combine per step into tmp_results: same operands, same order, same bits.
-int rs_recursive_halving_multipath(const char *sb, char *rb, const std::vector<size_t> &cnts,
-                                   MPIX_Datatype dt, MPIX_Op op, MPIX_Comm c, char *ws,
-                                   hipStream_t s, size_t ext)
+// The pair fold's prologue (Fold, coll_sched.h): the rank of a pair that drops
+// out sends its whole vector `acc`, the one that stays receives it into tmp
+// and folds it in -- and its epilogue, which hands the finished vector back.
+int fold_in(MPIX_Comm c, const Fold &f, char *acc, char *tmp, size_t count, MPIX_Datatype dt,
+            MPIX_Op op, hipStream_t s, size_t ext)
 {
-    const int rank = c->rank, size = c->size;
-    const size_t rc = cnts[0], total = rc * size;
+    if (!f.paired)
+        return MPIX_REDOP_SUCCESS;
+    if (f.newrank < 0)
+        return exchange(c, {snd(c->rank ^ 1, acc, count * ext)}, s);
+    TRY(exchange(c, {rcv(c->rank ^ 1, tmp, count * ext)}, s));
+    return combine(c, tmp, acc, (MPIX_Aint) count, dt, op, s);
+}
+
+int fold_out(MPIX_Comm c, const Fold &f, char *rb, size_t nb, hipStream_t s)
+{
+    if (!f.paired)
+        return MPIX_REDOP_SUCCESS;
+    return exchange(c, {f.newrank < 0 ? rcv(c->rank ^ 1, rb, nb) : snd(c->rank ^ 1, rb, nb)}, s);
+}
+
+// MPI_IN_PLACE tails: this rank's finished block `acc` lies inside recvbuf and
+// moves to its front.  With uneven counts the two can overlap; device copies
+// must not, so that one goes through `bounce` (host: a plain memmove).
+int move_block_to_front(MPIX_Comm c, char *rb, const char *acc, size_t blk, bool overlaps,
+                        char *bounce, hipStream_t s)
+{
+    if (!overlaps || c->host())
+        return copy(c, rb, acc, blk, s);
+    TRY(copy(c, bounce, acc, blk, s));
+    return copy(c, rb, bounce, blk, s);
+}
+
+// MPIR_Reduce_scatter_intra_recursive_halving
+// (reduce_scatter_intra_recursive_halving.c:38-260; the _block variant,
+// reduce_scatter_block_intra_recursive_halving.c:38-260, is the case of
+// equal counts).  cnts[i] = elements of rank i's result block.
+// `multipath` (MPIX_RSB_RECURSIVE_HALVING_MULTIPATH, multipath_shape() only):
+// every exchange step spread over all links (multipath_exchange), its relay
+// slots behind tmp_recvbuf -- same operands, same order, same bits.
+int rs_recursive_halving(const char *sb, char *rb, const std::vector<size_t> &cnts,
+                         MPIX_Datatype dt, MPIX_Op op, MPIX_Comm c, char *ws, hipStream_t s,
+                         size_t ext, bool multipath = false)
+{
+    const int rank = c->rank;
+    const Blocks old(cnts);
+    const size_t total = old.total;
+    if (!total)
+        return MPIX_REDOP_SUCCESS;
+    if (!multipath && rh_overlap_applies(c, cnts, ext))
+        return rs_recursive_halving_overlap(sb, rb, cnts[0], dt, op, c, ws, s, ext);
     char *tmp_results = ws;
     char *tmp_recvbuf = ws + round256(total * ext);
-    char *relay = tmp_recvbuf + round256(total * ext);     // (P/2 - 1) part slots
-    const size_t slot = round256(rc * ext);                 // a part is at most one block
-    // as rs_recursive_halving with P a power of two: the first step reads
-    // sendbuf, the last writes this rank's block into recvbuf (no copies)
+    char *relay = multipath ? tmp_recvbuf + round256(total * ext) : nullptr;   // (P/2 - 1) part slots
+    const size_t slot = round256(cnts[0] * ext);            // a part is at most one block
+    const Fold f(rank, c->size, true);
+    const int pof2 = f.pof2, newrank = f.newrank;
+    // P a power of two: no up-front copy of sendbuf into tmp_results (:91-96);
+    // the first step reads its halves from sendbuf and writes the combined
+    // half into tmp_results, the last writes this rank's block into recvbuf
+    // -- the same operands in the same roles, one HBM pass of the whole
+    // vector less
+    const bool direct = f.rem == 0;
     TRY(mark(c, "start", s));
-    int mask = size >> 1, send_idx = 0, recv_idx = 0;
-    bool in_rb = false;
-    while (mask > 0) {
-        if (rank < (rank ^ mask))
-            send_idx = recv_idx + mask;
-        else
-            recv_idx = send_idx + mask;
-        const size_t D = (size_t) mask * rc;             // both halves, every rank
-        const char *cur = mask == size >> 1 ? sb : tmp_results;
-        char *rbase = tmp_recvbuf + (size_t) recv_idx * rc * ext;
-        TRY(multipath_exchange(c, cur + (size_t) send_idx * rc * ext, rbase, D, mask, relay, slot,
-                               s, ext));
-        TRY(mark(c, "exchange", s));
-        char *out = tmp_results + (size_t) recv_idx * rc * ext;
-        if (mask == 1 && recv_idx == rank) {
-            out = rb;
-            in_rb = true;
-        }
-        TRY(combine_to(c, cur + (size_t) recv_idx * rc * ext, rbase, out, (MPIX_Aint) D, dt, op, s,
-                       ext));
-        TRY(mark(c, "combine", s));
-        send_idx = recv_idx;
-        mask >>= 1;
+    if (!direct) {
+        TRY(copy(c, tmp_results, sb, total * ext, s));                     // :91-96
+        TRY(mark(c, "local copy", s));
     }
-    if (!in_rb)
-        TRY(copy(c, rb, tmp_results + (size_t) rank * rc * ext, rc * ext, s));   // :232-240
+    if (f.paired) {                                                         // :110-137
+        TRY(fold_in(c, f, tmp_results, tmp_recvbuf, total, dt, op, s, ext));
+        TRY(mark(c, "prologue", s));
+    }
+    if (newrank != -1) {                                                    // :139-229
+        const Blocks folded(direct ? std::vector<size_t>() : f.newcnts(cnts));
+        const Blocks &nb = direct ? old : folded;   // no fold: the new ranks' blocks are the old
+        Window win{0, pof2};
+        bool in_rb = false;         // this rank's block already written to recvbuf
+        for (int mask = pof2 >> 1; mask > 0; mask >>= 1) {
+            const int newdst = newrank ^ mask, dst = f.real(newdst);
+            const Step st = halve(&win, newrank < newdst);
+            const size_t send_cnt = nb.range(st.send_lo, st.send_hi);
+            const size_t recv_cnt = nb.range(st.recv_lo, st.recv_hi);
+            const size_t soff = nb.disps[st.send_lo] * ext, roff = nb.disps[st.recv_lo] * ext;
+            const char *cur = direct && mask == pof2 >> 1 ? sb : tmp_results;
+            // zero-length legs are skipped on both sides (:188-208)
+            if (multipath)
+                TRY(multipath_exchange(c, cur + soff, tmp_recvbuf + roff, send_cnt, mask, relay,
+                                       slot, s, ext));
+            else
+                TRY(exchange(c, {snd(dst, cur + soff, send_cnt * ext),
+                                 rcv(dst, tmp_recvbuf + roff, recv_cnt * ext)}, s));
+            TRY(mark(c, "exchange", s));
+            char *out = tmp_results + roff;
+            const char *own = cur + roff;
+            const size_t nbytes = recv_cnt * ext;
+            // the last step's half is this rank's block: written straight into
+            // recvbuf, unless that would overwrite the half being read -- with
+            // MPI_IN_PLACE at P = 2 the first step is the last and reads
+            // recvbuf itself ([disps[1], +c1) against [0, c1) at rank 1)
+            if (direct && mask == 1 && st.recv_lo == newrank &&
+                (own == rb || own + nbytes <= rb || rb + nbytes <= own)) {
+                out = rb;
+                in_rb = true;
+            }
+            TRY(combine_to(c, own, tmp_recvbuf + roff, out, (MPIX_Aint) recv_cnt, dt, op, s, ext));
+            TRY(mark(c, "combine", s));
+        }
+        if (!in_rb)
+            TRY(copy(c, rb, tmp_results + old.disps[rank] * ext, cnts[rank] * ext, s));   // :232-240
+    }
+    if (f.paired) {                                                         // :245-262
+        if (rank % 2)
+            TRY(exchange(c, {snd(rank - 1, tmp_results + old.disps[rank - 1] * ext,
+                                 cnts[rank - 1] * ext)}, s));
+        else
+            TRY(exchange(c, {rcv(rank + 1, rb, cnts[rank] * ext)}, s));
+    }
     TRY(mark(c, "epilogue", s));
     return MPIX_REDOP_SUCCESS;
 }
@@ -1041,9 +951,8 @@ int rs_pairwise(const char *sb, char *rb, const std::vector<size_t> &cnts, MPIX_
                 MPIX_Op op, MPIX_Comm c, char *ws, hipStream_t s, size_t ext, bool concurrent)
 {
     const int rank = c->rank, size = c->size;
-    std::vector<size_t> disps(size, 0);
-    for (int i = 1; i < size; ++i)
-        disps[i] = disps[i - 1] + cnts[i - 1];
+    const Blocks b(cnts);
+    const std::vector<size_t> &disps = b.disps;
     const size_t blk = cnts[rank] * ext, sstride = round256(blk);
     const bool in_place = sb == rb;
     char *acc = in_place ? rb + disps[rank] * ext : rb;
@@ -1072,16 +981,8 @@ int rs_pairwise(const char *sb, char *rb, const std::vector<size_t> &cnts, MPIX_
             TRY(combine_multi(c, ins, acc, (MPIX_Aint) cnts[rank], dt, op, s));
         TRY(mark(c, "combine", s));
     }
-    if (in_place && rank != 0) {
-        // with uneven counts the own block can overlap the front of recvbuf;
-        // device copies must not overlap, so go through the (free) workspace
-        if (disps[rank] * ext < blk && !c->host()) {
-            TRY(copy(c, ws, acc, blk, s));
-            TRY(copy(c, rb, ws, blk, s));
-        } else {
-            TRY(copy(c, rb, acc, blk, s));
-        }
-    }
+    if (in_place && rank != 0)      // the workspace is free by now
+        TRY(move_block_to_front(c, rb, acc, blk, disps[rank] * ext < blk, ws, s));
     return MPIX_REDOP_SUCCESS;
 }
 
@@ -1097,28 +998,21 @@ int rs_pairwise_pipelined(const char *sb, char *rb, const std::vector<size_t> &c
 {
     const int rank = c->rank, size = c->size;
     const size_t blk = cnts[rank] * ext;
-    // the chunk count must be the same on every rank (both ends of a message
-    // cut it alike), so it follows the largest block: chunks of >= 4 MiB of
-    // it, at most kPipeChunks
     size_t maxblk = 0;
     for (size_t n : cnts)
         maxblk = n * ext > maxblk ? n * ext : maxblk;
-    if (c->host() || c->combine || size == 1 || maxblk < (size_t(8) << 20))
+    const size_t nch = pipe_chunks(maxblk);     // the same on every rank
+    if (c->host() || c->combine || size == 1 || nch < 2)
         return rs_pairwise(sb, rb, cnts, dt, op, c, ws, s, ext, true);
-    constexpr size_t kPipeChunks = 8;
-    size_t nch = maxblk >> 22;
-    if (nch > kPipeChunks)
-        nch = kPipeChunks;
     TRY(ensure_aux(c, nch + 1));
-    std::vector<size_t> disps(size, 0);
-    for (int i = 1; i < size; ++i)
-        disps[i] = disps[i - 1] + cnts[i - 1];
+    const Blocks b(cnts);
+    const std::vector<size_t> &disps = b.disps;
     const size_t sstride = round256(blk);
     const bool in_place = sb == rb;
     char *acc = in_place ? rb + disps[rank] * ext : rb;
     if (!in_place)
         TRY(copy(c, rb, sb + disps[rank] * ext, blk, s));
-    auto lo = [nch](size_t n, size_t k) { return n * k / nch; };    // chunk k: [lo(k), lo(k+1))
+    auto lo = [nch](size_t n, size_t k) { return pipe_lo(n, k, nch); };
     for (size_t k = 0; k < nch; ++k) {
         std::vector<MPIX_P2p_op> ops;
         std::vector<const void *> ins;
@@ -1139,19 +1033,10 @@ int rs_pairwise_pipelined(const char *sb, char *rb, const std::vector<size_t> &c
     }
     HTRY(hipEventRecord(c->pipe_ev[nch], c->aux));
     HTRY(hipStreamWaitEvent(s, c->pipe_ev[nch], 0));
-    if (in_place && rank != 0) {
-        if (disps[rank] * ext < blk) {
-            TRY(copy(c, ws, acc, blk, s));
-            TRY(copy(c, rb, ws, blk, s));
-        } else {
-            TRY(copy(c, rb, acc, blk, s));
-        }
-    }
+    if (in_place && rank != 0)
+        TRY(move_block_to_front(c, rb, acc, blk, disps[rank] * ext < blk, ws, s));
     return MPIX_REDOP_SUCCESS;
 }
-
-size_t rs_workspace(size_t total, size_t mine, size_t ext, int size, int algo);
-int bitrev(int r, int pof2);
 
 // ---- pull windows --------------------------------------------------------
 // The pulls read peers' memory directly.  Ranks that are threads of one
@@ -1481,6 +1366,82 @@ int shared_direct(MPIX_Comm c, int n, const void *const *ps, const size_t *bytes
     return MPIX_REDOP_SUCCESS;
 }
 
+// Where a pull reads every rank's buffers: bases[i][q] is rank q's i-th buffer.
+struct Published {
+    std::vector<const char *> bases[2];
+    bool ok = true;             // false (every rank): no pull windows, run the transport form
+    bool used_win = false;
+    char *win_own = nullptr;    // the window's copy of the range only the owner reads
+};
+
+// Make this rank's n (1 or 2) buffers of nb bytes readable by its peers, by
+// one of three routes.  Threads of one process: the raw addresses are
+// all-gathered once the stream has finished writing the inputs.  Buffers that
+// every rank holds in the same shared windows: read in place.  Otherwise
+// bufs[0] is copied into the pull window, but for its bytes [own_lo, own_hi)
+// that only this rank reads (own_lo == own_hi == nb: all of it), and a
+// stream-ordered barrier follows; every buffer of a peer is then its window.
+int publish_for_pull(MPIX_Comm c, int n, const char *const *bufs, size_t nb, size_t own_lo,
+                     size_t own_hi, hipStream_t s, Published *p)
+{
+    const int rank = c->rank, size = c->size;
+    for (int i = 0; i < n; ++i)
+        p->bases[i].assign(size, bufs[i]);
+    if (c->kind == K_LOCAL_DEV) {
+        LocalRec me[2];
+        static_assert(sizeof me <= kRec, "pull records");
+        for (int i = 0; i < n; ++i)
+            me[i] = LocalRec{1, 0, reinterpret_cast<uint64_t>(bufs[i])};
+        HTRY(hipStreamSynchronize(s));  // this rank's inputs complete before anyone reads them
+        std::vector<char> all;
+        TRY(allgather_records(c, me, (size_t) n * sizeof(LocalRec), &all, s));
+        for (int q = 0; q < size; ++q) {
+            LocalRec r[2];
+            memcpy(r, all.data() + kRec * (size_t) q, sizeof r);
+            for (int i = 0; i < n; ++i)
+                p->bases[i][q] = reinterpret_cast<const char *>(r[i].raw);
+        }
+        return MPIX_REDOP_SUCCESS;
+    }
+    bool direct;
+    std::vector<int64_t> where;
+    const void *ps[2] = {bufs[0], n > 1 ? bufs[1] : nullptr};
+    const size_t nbs[2] = {nb, nb};
+    TRY(shared_direct(c, n, ps, nbs, s, &direct, &where));
+    if (direct) {
+        for (int i = 0; i < n; ++i)
+            for (int q = 0; q < size; ++q)
+                if (q != rank)
+                    p->bases[i][q] = static_cast<const char *>(c->shared[where[2 * i]].maps[q]) +
+                                     kWinHdr + where[2 * i + 1];
+        return MPIX_REDOP_SUCCESS;
+    }
+    TRY(ensure_windows(c, nb, s, &p->ok));
+    if (!p->ok)
+        return MPIX_REDOP_SUCCESS;
+    p->used_win = true;
+    char *wd = c->win + kWinHdr;
+    TRY(copy(c, wd, bufs[0], own_lo, s));
+    TRY(copy(c, wd + own_hi, bufs[0] + own_hi, nb - own_hi, s));
+    p->win_own = wd + own_lo;
+    TRY(barrier(c, s));                 // every window filled
+    for (int i = 0; i < n; ++i)
+        for (int q = 0; q < size; ++q)
+            if (q != rank)
+                p->bases[i][q] = static_cast<const char *>(c->peer_map[q]) + kWinHdr;
+    return MPIX_REDOP_SUCCESS;
+}
+
+// the pull's closing barrier on the stream: no rank reuses its window /
+// buffers before all peers have read them; the window's next user waits for it
+int pull_done(MPIX_Comm c, const Published &p, hipStream_t s)
+{
+    TRY(barrier(c, s));
+    if (p.used_win)
+        HTRY(hipEventRecord(c->win_ev, s));
+    return MPIX_REDOP_SUCCESS;
+}
+
 // MPIX_RSB_PULL: the pairwise schedule with the transport and the receive
 // buffers folded into the combine.  Every rank's inputs become readable by
 // its peers -- in its pull window (another process: copied in, then a
@@ -1502,12 +1463,8 @@ int rs_pull(const char *sb, char *rb, const std::vector<size_t> &cnts, MPIX_Data
             MPIX_Comm c, hipStream_t s, size_t ext, bool tree = false)
 {
     const int rank = c->rank, size = c->size;
-    std::vector<size_t> disps(size, 0);
-    for (int i = 1; i < size; ++i)
-        disps[i] = disps[i - 1] + cnts[i - 1];
-    size_t total = 0;
-    for (size_t n : cnts)
-        total += n;
+    const Blocks b(cnts);
+    const size_t total = b.total;
     auto fallback = [&]() -> int {     // same bits: one-group pairwise / recursive halving
         const int alg = tree ? MPIX_RSB_RECURSIVE_HALVING : MPIX_RSB_PAIRWISE;
         ran_instead(c, &c->last_rs, alg);
@@ -1520,75 +1477,33 @@ int rs_pull(const char *sb, char *rb, const std::vector<size_t> &cnts, MPIX_Data
     };
     if (c->host() || c->combine || size > 16 || !c->pulls_possible())
         return fallback();
-    const size_t blk = cnts[rank] * ext;
+    const size_t blk = cnts[rank] * ext, own = b.disps[rank] * ext;
     const bool in_place = sb == rb;
-    char *acc = in_place ? rb + disps[rank] * ext : rb;
+    char *acc = in_place ? rb + own : rb;
     TRY(mark(c, "start", s));
-    std::vector<const char *> bases(size, sb);  // where each rank's inputs are read
-    bool used_win = false;
-    if (c->kind == K_LOCAL_DEV) {
-        // threads of one process: the user buffers themselves
-        LocalRec me{1, 0, reinterpret_cast<uint64_t>(sb)};
-        HTRY(hipStreamSynchronize(s));  // this rank's inputs complete before anyone reads them
-        std::vector<char> all;
-        TRY(allgather_records(c, &me, sizeof me, &all, s));
-        for (int q = 0; q < size; ++q) {
-            LocalRec r;
-            memcpy(&r, all.data() + kRec * (size_t) q, sizeof r);
-            bases[q] = reinterpret_cast<const char *>(r.raw);
-        }
-    } else {
-        bool direct;
-        std::vector<int64_t> where;
-        const void *ps[1] = {sb};
-        const size_t nbs[1] = {total * ext};
-        TRY(shared_direct(c, 1, ps, nbs, s, &direct, &where));
-        if (direct) {                   // every rank's input in a shared window: read in place
-            for (int q = 0; q < size; ++q)
-                if (q != rank)
-                    bases[q] = static_cast<const char *>(c->shared[where[0]].maps[q]) + kWinHdr +
-                               where[1];
-        } else {
-            bool ok;
-            TRY(ensure_windows(c, total * ext, s, &ok));
-            if (!ok)
-                return fallback();
-            used_win = true;
-            // the blocks the peers read (this rank's own block is read from sb)
-            char *wd = c->win + kWinHdr;
-            TRY(copy(c, wd, sb, disps[rank] * ext, s));
-            TRY(copy(c, wd + (disps[rank] + cnts[rank]) * ext, sb + (disps[rank] + cnts[rank]) * ext,
-                     (total - disps[rank] - cnts[rank]) * ext, s));
-            TRY(barrier(c, s));         // every window filled
-            for (int q = 0; q < size; ++q)
-                if (q != rank)
-                    bases[q] = static_cast<const char *>(c->peer_map[q]) + kWinHdr;
-        }
-    }
+    // the blocks the peers read (this rank's own block is read from sb)
+    Published pub;
+    const char *const bufs[1] = {sb};
+    TRY(publish_for_pull(c, 1, bufs, total * ext, own, own + blk, s, &pub));
+    if (!pub.ok)
+        return fallback();
+    const std::vector<const char *> &bases = pub.bases[0];
     if (!in_place && !tree)
-        TRY(copy(c, rb, sb + disps[rank] * ext, blk, s));                   // :58-64
+        TRY(copy(c, rb, sb + own, blk, s));                                 // :58-64
     std::vector<const void *> ins;
     if (tree) {
-        // slot s: rank ^ bitrev(s) (P a power of two); otherwise the
-        // reference's fold (:110-137) is the first level -- slot pair (2t, 2t+1)
-        // is new rank v = nr ^ bitrev(t): inout the odd rank 2v + 1, in the even
-        // 2v, or new rank v's own input alone -- and its block holds this rank's
-        const int pof2 = pof2_of(size), rem = size - pof2;
-        const int nr = rank < 2 * rem ? rank / 2 : rank - rem;
-        const int k = rem ? 2 * pof2 : pof2;
-        for (int sl = 0; sl < k; ++sl) {
-            int src;
-            if (!rem) {
-                src = rank ^ bitrev(sl, size);
-            } else {
-                const int v = nr ^ bitrev(sl / 2, pof2), j = sl % 2;
-                src = v < rem ? (j ? 2 * v : 2 * v + 1) : (j ? -1 : v + rem);
-            }
-            ins.push_back(src < 0 ? nullptr : bases[src] + disps[rank] * ext);
+        // the tree follows recursive halving's decreasing masks (slot t is
+        // new rank nr ^ bitrev(t)); a rank the fold drops computes its block
+        // too, as new rank rank / 2 -- its block holds this rank's
+        const Fold f(rank, size, true);
+        const int nr = f.paired ? rank / 2 : f.newrank;
+        for (int sl = 0; sl < tree_slots(f.pof2, f.rem); ++sl) {
+            const int src = tree_slot_source(nr, sl, f.pof2, f.rem, true);
+            ins.push_back(src < 0 ? nullptr : bases[src] + own);
         }
     } else {
         for (int i = 1; i < size; ++i)
-            ins.push_back(bases[(rank - i + size) % size] + disps[rank] * ext);
+            ins.push_back(bases[(rank - i + size) % size] + own);
     }
     TRY(mark(c, "publish", s));
     if (cnts[rank] && tree)
@@ -1597,80 +1512,16 @@ int rs_pull(const char *sb, char *rb, const std::vector<size_t> &cnts, MPIX_Data
     else if (cnts[rank])
         TRY(combine_multi(c, ins, acc, (MPIX_Aint) cnts[rank], dt, op, s));
     TRY(mark(c, "pull+combine", s));
-    TRY(barrier(c, s));                 // peers done reading this rank's buffer / window
-    if (used_win)
-        HTRY(hipEventRecord(c->win_ev, s));
+    TRY(pull_done(c, pub, s));          // peers done reading this rank's buffer / window
     if (in_place && rank != 0) {
-        if (disps[rank] * ext < blk) {
-            char *w;
+        const bool overlaps = own < blk;
+        char *w = nullptr;
+        if (overlaps)
             TRY(scratch(c, round256(blk), s, &w));
-            TRY(copy(c, w, acc, blk, s));
-            TRY(copy(c, rb, w, blk, s));
-            TRY(release_scratch(c, w, MPIX_REDOP_SUCCESS, s));
-        } else {
-            TRY(copy(c, rb, acc, blk, s));
-        }
+        TRY(move_block_to_front(c, rb, acc, blk, overlaps, w, s));
+        TRY(release_scratch(c, w, MPIX_REDOP_SUCCESS, s));
     }
     return MPIX_REDOP_SUCCESS;
-}
-
-// generic.json:277-291 / :316-341: recursive halving below 512 KiB of total
-// message, pairwise above (commutative ops)
-int rs_choose(int algorithm, size_t total_bytes)
-{
-    if (algorithm != MPIX_RSB_AUTO)
-        return algorithm;
-    return total_bytes < (512u << 10) ? MPIX_RSB_RECURSIVE_HALVING : MPIX_RSB_PAIRWISE;
-}
-
-int rsb_choose(int algorithm, size_t recvcount, size_t ext, int size)
-{
-    return rs_choose(algorithm, recvcount * ext * size);
-}
-
-// scratch bytes of a schedule: total = all ranks' elements, mine = this
-// rank's result elements
-size_t rs_workspace(size_t total, size_t mine, size_t ext, int size, int algo)
-{
-    if (size == 1)
-        return 0;
-    switch (algo) {
-        case MPIX_RSB_RECURSIVE_HALVING:
-            return 2 * round256(total * ext);
-        case MPIX_RSB_RECURSIVE_HALVING_MULTIPATH:   // + the relay slots (total = size * mine)
-            return 2 * round256(total * ext) +
-                   (total == mine * (size_t) size ? multipath_relay_bytes(mine, ext, size) : 0);
-        case MPIX_RSB_PAIRWISE:
-        case MPIX_RSB_PAIRWISE_PIPELINED:
-            return (size - 1) * round256(mine * ext);
-        case MPIX_RSB_PAIRWISE_SEQUENTIAL:
-            return round256(mine * ext);
-        case MPIX_RSB_RECURSIVE_HALVING_PULL:       // P > 16 runs RECURSIVE_HALVING
-            return size > 16 ? 2 * round256(total * ext) : 0;
-        default:
-            return 0;
-    }
-}
-
-// MPI_Reduce: tmp_buf, plus the accumulator a non-root rank has no recvbuf for
-size_t reduce_workspace(size_t nb, bool is_root)
-{
-    return round256(nb) + (is_root ? 0 : round256(nb));
-}
-
-size_t rsb_workspace(size_t recvcount, size_t ext, int size, int algo)
-{
-    return rs_workspace(recvcount * size, recvcount, ext, size, algo);
-}
-
-int bitrev(int r, int pof2)
-{
-    int out = 0;
-    for (int b = pof2 >> 1; b; b >>= 1) {
-        out = (out << 1) | (r & 1);
-        r >>= 1;
-    }
-    return out;
 }
 
 // MPIR_Allreduce_intra_reduce_scatter_allgather
@@ -1684,69 +1535,34 @@ int bitrev(int r, int pof2)
 int allreduce_rsag(char *rb, size_t count, MPIX_Datatype dt, MPIX_Op op, MPIX_Comm c, char *tmp,
                    hipStream_t s, size_t ext, bool direct, bool multipath = false)
 {
-    const int rank = c->rank, size = c->size;
-    const int pof2 = pof2_of(size), rem = size - pof2;
+    const Fold f(c->rank, c->size, true);
+    const int pof2 = f.pof2, newrank = f.newrank;
     const size_t nb = count * ext;
-    int newrank;
-    if (rank < 2 * rem) {                                                   // :85-112
-        if (rank % 2 == 0) {
-            TRY(exchange(c, {snd(rank + 1, rb, nb)}, s));
-            newrank = -1;
-        } else {
-            TRY(exchange(c, {rcv(rank - 1, tmp, nb)}, s));
-            TRY(combine(c, tmp, rb, (MPIX_Aint) count, dt, op, s));
-            newrank = rank / 2;
-        }
-    } else {
-        newrank = rank - rem;
-    }
+    TRY(fold_in(c, f, rb, tmp, count, dt, op, s, ext));                     // :85-112
     if (newrank != -1) {
-        std::vector<size_t> cnts(pof2), disps(pof2, 0);
-        for (int i = 0; i < pof2; ++i)
-            cnts[i] = count / pof2 + ((size_t) i < count % pof2 ? 1 : 0);
-        for (int i = 1; i < pof2; ++i)
-            disps[i] = disps[i - 1] + cnts[i - 1];
-        auto sum = [&](int lo, int hi) {
-            size_t t = 0;
-            for (int i = lo; i < hi; ++i)
-                t += cnts[i];
-            return t;
-        };
-        auto real = [&](int nr) { return nr < rem ? nr * 2 + 1 : nr + rem; };
-        int mask = 1, send_idx = 0, recv_idx = 0, last_idx = pof2;
+        const Blocks b = Blocks::even(count, pof2);
+        Window win{0, pof2};
         int mp_steps = 0;           // reduce-scatter steps that ran over the relays
-        while (mask < pof2) {                                               // :138-189
-            int newdst = newrank ^ mask;
-            size_t send_cnt, recv_cnt;
-            if (newrank < newdst) {
-                send_idx = recv_idx + pof2 / (mask * 2);
-                send_cnt = sum(send_idx, last_idx);
-                recv_cnt = sum(recv_idx, send_idx);
-            } else {
-                recv_idx = send_idx + pof2 / (mask * 2);
-                send_cnt = sum(send_idx, recv_idx);
-                recv_cnt = sum(recv_idx, last_idx);
-            }
+        for (int mask = 1; mask < pof2; mask <<= 1) {                       // :138-189
+            const int newdst = newrank ^ mask;
+            const Step st = halve(&win, newrank < newdst);
+            const size_t send_cnt = b.range(st.send_lo, st.send_hi);
+            const size_t recv_cnt = b.range(st.recv_lo, st.recv_hi);
+            const size_t soff = b.disps[st.send_lo] * ext, roff = b.disps[st.recv_lo] * ext;
             const size_t parts = (size_t) pof2 / 2;
-            const bool mp_step = multipath && rem == 0 && pof2 >= 4 && count % pof2 == 0 &&
+            const bool mp_step = multipath && f.rem == 0 && pof2 >= 4 && count % pof2 == 0 &&
                                  send_cnt >= parts * (parts - 1);
             if (mp_step) {
                 ++mp_steps;
                 // send_cnt == recv_cnt here; relay slots fit in send_cnt elements
                 const size_t slot = (send_cnt + parts - 1) / parts * ext;
-                TRY(multipath_exchange(c, rb + disps[send_idx] * ext, tmp + disps[recv_idx] * ext,
-                                       send_cnt, mask, tmp + disps[send_idx] * ext, slot, s, ext));
+                TRY(multipath_exchange(c, rb + soff, tmp + roff, send_cnt, mask, tmp + soff, slot,
+                                       s, ext));
             } else {
-                TRY(exchange(c, {snd(real(newdst), rb + disps[send_idx] * ext, send_cnt * ext),
-                                 rcv(real(newdst), tmp + disps[recv_idx] * ext, recv_cnt * ext)},
-                             s));
+                TRY(exchange(c, {snd(f.real(newdst), rb + soff, send_cnt * ext),
+                                 rcv(f.real(newdst), tmp + roff, recv_cnt * ext)}, s));
             }
-            TRY(combine(c, tmp + disps[recv_idx] * ext, rb + disps[recv_idx] * ext,
-                        (MPIX_Aint) recv_cnt, dt, op, s));
-            send_idx = recv_idx;
-            mask <<= 1;
-            if (mask < pof2)
-                last_idx = recv_idx + pof2 / mask;
+            TRY(combine(c, tmp + roff, rb + roff, (MPIX_Aint) recv_cnt, dt, op, s));
         }
         // a step too small for the relay slots runs the plain exchange (the
         // last, smallest steps first); the call counts as MULTIPATH while its
@@ -1754,48 +1570,28 @@ int allreduce_rsag(char *rb, size_t count, MPIX_Datatype dt, MPIX_Op op, MPIX_Co
         // and as the plain schedule only when no step did
         if (multipath && !mp_steps)
             ran_instead(c, &c->last_ar, MPIX_ALLREDUCE_REDUCE_SCATTER_ALLGATHER);
-        mask >>= 1;
         if (direct) {
             const int mine = bitrev(newrank, pof2);
             std::vector<MPIX_P2p_op> ops;
             for (int q = 0; q < pof2; ++q) {
                 if (q == newrank)
                     continue;
-                const int b = bitrev(q, pof2);
-                ops.push_back(snd(real(q), rb + disps[mine] * ext, cnts[mine] * ext));
-                ops.push_back(rcv(real(q), rb + disps[b] * ext, cnts[b] * ext));
+                const int bq = bitrev(q, pof2);
+                ops.push_back(snd(f.real(q), rb + b.disps[mine] * ext, b.cnt(mine) * ext));
+                ops.push_back(rcv(f.real(q), rb + b.disps[bq] * ext, b.cnt(bq) * ext));
             }
             TRY(exchange(c, ops, s));
-            mask = 0;
         }
-        while (mask > 0) {                                                  // :191-226
-            int newdst = newrank ^ mask;
-            size_t send_cnt, recv_cnt;
-            if (newrank < newdst) {
-                if (mask != pof2 / 2)
-                    last_idx = last_idx + pof2 / (mask * 2);
-                recv_idx = send_idx + pof2 / (mask * 2);
-                send_cnt = sum(send_idx, recv_idx);
-                recv_cnt = sum(recv_idx, last_idx);
-            } else {
-                recv_idx = send_idx - pof2 / (mask * 2);
-                send_cnt = sum(send_idx, last_idx);
-                recv_cnt = sum(recv_idx, send_idx);
-            }
-            TRY(exchange(c, {snd(real(newdst), rb + disps[send_idx] * ext, send_cnt * ext),
-                             rcv(real(newdst), rb + disps[recv_idx] * ext, recv_cnt * ext)}, s));
-            if (newrank > newdst)
-                send_idx = recv_idx;
-            mask >>= 1;
+        for (int mask = direct ? 0 : pof2 >> 1; mask > 0; mask >>= 1) {     // :191-226
+            const int newdst = newrank ^ mask;
+            const Step st = regrow(&win, newrank < newdst);
+            TRY(exchange(c, {snd(f.real(newdst), rb + b.disps[st.send_lo] * ext,
+                                 b.range(st.send_lo, st.send_hi) * ext),
+                             rcv(f.real(newdst), rb + b.disps[st.recv_lo] * ext,
+                                 b.range(st.recv_lo, st.recv_hi) * ext)}, s));
         }
     }
-    if (rank < 2 * rem) {                                                   // :229-238
-        if (rank % 2)
-            TRY(exchange(c, {snd(rank - 1, rb, nb)}, s));
-        else
-            TRY(exchange(c, {rcv(rank + 1, rb, nb)}, s));
-    }
-    return MPIX_REDOP_SUCCESS;
+    return fold_out(c, f, rb, nb, s);                                       // :229-238
 }
 
 // MPIX_ALLREDUCE_PULL: the Rabenseifner allreduce's association (same bits as
@@ -1810,9 +1606,6 @@ int allreduce_rsag(char *rb, size_t count, MPIX_Datatype dt, MPIX_Op op, MPIX_Co
 // (MPIX_Copy_multi_async).  A closing barrier keeps every rank's window /
 // buffers in place until its peers are done.  No workspace.  Other shapes:
 // the sendbuf copy + REDUCE_SCATTER_ALLGATHER.
-int allreduce_rsag(char *rb, size_t count, MPIX_Datatype dt, MPIX_Op op, MPIX_Comm c, char *tmp,
-                   hipStream_t s, size_t ext, bool direct, bool multipath);
-
 int allreduce_pull(const char *sendbuf, char *rb, size_t count, MPIX_Datatype dt, MPIX_Op op,
                    MPIX_Comm c, void *ws, size_t ws_bytes, hipStream_t s, size_t ext)
 {
@@ -1833,92 +1626,33 @@ int allreduce_pull(const char *sendbuf, char *rb, size_t count, MPIX_Datatype dt
     // the reference's layout (:85-127): P - pof2 even/odd pairs fold first (the
     // odd rank keeps going as new rank i), then pof2 new ranks share pof2
     // blocks; new rank v owns block bitrev(v)
-    const int pof2 = pof2_of(size), rem = size - pof2;
-    std::vector<size_t> cnts(pof2), disps(pof2, 0);
-    for (int i = 0; i < pof2; ++i)
-        cnts[i] = count / pof2 + ((size_t) i < count % pof2 ? 1 : 0);
-    for (int i = 1; i < pof2; ++i)
-        disps[i] = disps[i - 1] + cnts[i - 1];
-    auto real = [rem](int v) { return v < rem ? 2 * v + 1 : v + rem; };
-    const int nr = rank < 2 * rem ? (rank % 2 ? rank / 2 : -1) : rank - rem;
+    const Fold f(rank, size, true);
+    const int pof2 = f.pof2, nr = f.newrank;
+    const Blocks b = Blocks::even(count, pof2);
     const int mine = nr >= 0 ? bitrev(nr, pof2) : -1;     // -1: a folded-away even rank
-    // in_base[q]: where rank q's input is read; out_base[q]: where its
-    // reduced block is read in the allgather; out: where this rank's goes
-    std::vector<const char *> in_base(size, in), out_base(size, rb);
-    bool used_win = false;
-    char *out = mine >= 0 ? rb + disps[mine] * ext : nullptr;
+    const size_t own = mine >= 0 ? b.disps[mine] * ext : nb;
     TRY(mark(c, "start", s));
-    if (c->kind == K_LOCAL_DEV) {     // threads of one process: the user buffers
-        struct Recs {
-            LocalRec in, out;
-        } me{{1, 0, reinterpret_cast<uint64_t>(in)}, {1, 0, reinterpret_cast<uint64_t>(rb)}};
-        static_assert(sizeof(Recs) <= kRec, "allreduce pull records");
-        HTRY(hipStreamSynchronize(s));  // inputs complete before anyone reads them
-        std::vector<char> all;
-        TRY(allgather_records(c, &me, sizeof me, &all, s));
-        for (int q = 0; q < size; ++q) {
-            Recs r;
-            memcpy(&r, all.data() + kRec * (size_t) q, sizeof r);
-            in_base[q] = reinterpret_cast<const char *>(r.in.raw);
-            out_base[q] = reinterpret_cast<const char *>(r.out.raw);
-        }
-    } else {                            // processes
-        bool direct;
-        std::vector<int64_t> where;
-        const void *ps[2] = {in, rb};
-        const size_t nbs[2] = {nb, nb};
-        TRY(shared_direct(c, 2, ps, nbs, s, &direct, &where));
-        if (direct) {                   // input and result in shared windows: in place
-            for (int q = 0; q < size; ++q) {
-                if (q == rank)
-                    continue;
-                in_base[q] = static_cast<const char *>(c->shared[where[0]].maps[q]) + kWinHdr +
-                             where[1];
-                out_base[q] = static_cast<const char *>(c->shared[where[2]].maps[q]) + kWinHdr +
-                              where[3];
-            }
-        } else {                        // the pull windows
-            bool ok;
-            TRY(ensure_windows(c, nb, s, &ok));
-            if (!ok)
-                return fallback();
-            used_win = true;
-            char *wd = c->win + kWinHdr;
-            if (mine >= 0) {            // every block but this rank's own (only it reads that)
-                TRY(copy(c, wd, in, disps[mine] * ext, s));
-                TRY(copy(c, wd + (disps[mine] + cnts[mine]) * ext,
-                         in + (disps[mine] + cnts[mine]) * ext,
-                         nb - (disps[mine] + cnts[mine]) * ext, s));
-                out = wd + disps[mine] * ext;   // peers read it from the window
-            } else {
-                TRY(copy(c, wd, in, nb, s));
-            }
-            TRY(barrier(c, s));         // every window filled
-            for (int q = 0; q < size; ++q)
-                if (q != rank)
-                    in_base[q] = out_base[q] = static_cast<const char *>(c->peer_map[q]) + kWinHdr;
-        }
-    }
+    // pub.bases[0][q]: where rank q's input is read; [1][q]: where its reduced
+    // block is read in the allgather; out: where this rank's goes -- into the
+    // window, when that is where the peers read it (every block but this
+    // rank's own was copied there: only it reads that)
+    Published pub;
+    const char *const bufs[2] = {in, rb};
+    TRY(publish_for_pull(c, 2, bufs, nb, own, mine >= 0 ? own + b.cnt(mine) * ext : nb, s, &pub));
+    if (!pub.ok)
+        return fallback();
+    char *out = mine < 0 ? nullptr : pub.used_win ? pub.win_own : rb + own;
     TRY(mark(c, "publish", s));
-    if (mine >= 0 && cnts[mine]) {
-        // slot s of the tree: without a fold, rank nr ^ s (masks 1, 2, ...:
-        // :138-189); with one, slot pair (2t, 2t + 1) is new rank v = nr ^ t's
-        // fold -- inout the odd rank 2v + 1, in the even 2v (:94-108) -- or
-        // new rank v's own input alone
-        const int k = rem ? 2 * pof2 : pof2;
+    if (mine >= 0 && b.cnt(mine)) {
+        // slot t of the tree is new rank nr ^ t (masks 1, 2, ...: :138-189)
+        const int k = tree_slots(pof2, f.rem);
         std::vector<const void *> ins(k, nullptr);
         for (int sl = 0; sl < k; ++sl) {
-            int src;
-            if (!rem) {
-                src = nr ^ sl;
-            } else {
-                const int v = nr ^ (sl / 2), j = sl % 2;
-                src = v < rem ? (j ? 2 * v : 2 * v + 1) : (j ? -1 : v + rem);
-            }
+            const int src = tree_slot_source(nr, sl, pof2, f.rem, false);
             if (src >= 0)
-                ins[sl] = in_base[src] + disps[mine] * ext;
+                ins[sl] = pub.bases[0][src] + own;
         }
-        TRY(MPIX_Reduce_local_tree_async(ins.data(), k, out, (MPIX_Aint) cnts[mine], dt, op, s));
+        TRY(MPIX_Reduce_local_tree_async(ins.data(), k, out, (MPIX_Aint) b.cnt(mine), dt, op, s));
     }
     TRY(mark(c, "reduce-scatter pull", s));
     TRY(barrier(c, s));                 // every block final (and every input read)
@@ -1926,60 +1660,35 @@ int allreduce_pull(const char *sendbuf, char *rb, size_t count, MPIX_Datatype dt
     std::vector<void *> dsts;
     std::vector<MPIX_Aint> bytes;
     for (int v = 0; v < pof2; ++v) {
-        const int q = real(v), b = bitrev(v, pof2);
-        const char *src = q == rank ? out : out_base[q] + disps[b] * ext;
-        if (src == rb + disps[b] * ext)
+        const int q = f.real(v), bv = bitrev(v, pof2);
+        const char *src = q == rank ? out : pub.bases[1][q] + b.disps[bv] * ext;
+        if (src == rb + b.disps[bv] * ext)
             continue;                   // this rank's block already in place
         srcs.push_back(src);
-        dsts.push_back(rb + disps[b] * ext);
-        bytes.push_back((MPIX_Aint) (cnts[b] * ext));
+        dsts.push_back(rb + b.disps[bv] * ext);
+        bytes.push_back((MPIX_Aint) (b.cnt(bv) * ext));
     }
     for (size_t lo = 0; lo < srcs.size(); lo += 16) {
         const int n = (int) std::min<size_t>(16, srcs.size() - lo);
         TRY(MPIX_Copy_multi_async(srcs.data() + lo, dsts.data() + lo, bytes.data() + lo, n, s));
     }
     TRY(mark(c, "allgather pull", s));
-    TRY(barrier(c, s));                 // peers done reading this rank's window / buffers
-    if (used_win)
-        HTRY(hipEventRecord(c->win_ev, s));
-    return MPIX_REDOP_SUCCESS;
+    return pull_done(c, pub, s);        // peers done reading this rank's window / buffers
 }
 
 // MPIR_Allreduce_intra_recursive_doubling (allreduce_intra_recursive_doubling.c:24-150)
 int allreduce_rd(char *rb, size_t count, MPIX_Datatype dt, MPIX_Op op, MPIX_Comm c, char *tmp,
                  hipStream_t s, size_t ext)
 {
-    const int rank = c->rank, size = c->size;
-    const int pof2 = pof2_of(size), rem = size - pof2;
+    const Fold f(c->rank, c->size, true);
     const size_t nb = count * ext;
-    int newrank;
-    if (rank < 2 * rem) {                                                   // :59-86
-        if (rank % 2 == 0) {
-            TRY(exchange(c, {snd(rank + 1, rb, nb)}, s));
-            newrank = -1;
-        } else {
-            TRY(exchange(c, {rcv(rank - 1, tmp, nb)}, s));
-            TRY(combine(c, tmp, rb, (MPIX_Aint) count, dt, op, s));
-            newrank = rank / 2;
-        }
-    } else {
-        newrank = rank - rem;
+    TRY(fold_in(c, f, rb, tmp, count, dt, op, s, ext));                     // :59-86
+    for (int mask = 1; f.newrank != -1 && mask < f.pof2; mask <<= 1) {      // :97-129
+        const int dst = f.real(f.newrank ^ mask);
+        TRY(exchange(c, {snd(dst, rb, nb), rcv(dst, tmp, nb)}, s));
+        TRY(combine(c, tmp, rb, (MPIX_Aint) count, dt, op, s));
     }
-    if (newrank != -1) {
-        for (int mask = 1; mask < pof2; mask <<= 1) {                       // :97-129
-            int newdst = newrank ^ mask;
-            int dst = newdst < rem ? newdst * 2 + 1 : newdst + rem;
-            TRY(exchange(c, {snd(dst, rb, nb), rcv(dst, tmp, nb)}, s));
-            TRY(combine(c, tmp, rb, (MPIX_Aint) count, dt, op, s));
-        }
-    }
-    if (rank < 2 * rem) {                                                   // :131-141
-        if (rank % 2)
-            TRY(exchange(c, {snd(rank - 1, rb, nb)}, s));
-        else
-            TRY(exchange(c, {rcv(rank + 1, rb, nb)}, s));
-    }
-    return MPIX_REDOP_SUCCESS;
+    return fold_out(c, f, rb, nb, s);                                       // :131-141
 }
 
 // MPIR_Reduce_intra_binomial (reduce_intra_binomial.c:12-131) for the
@@ -2018,114 +1727,50 @@ int reduce_binomial(char *acc, size_t count, MPIX_Datatype dt, MPIX_Op op, int r
 int reduce_rsg(char *acc, size_t count, MPIX_Datatype dt, MPIX_Op op, int root, MPIX_Comm c,
                char *tmp, hipStream_t s, size_t ext)
 {
-    const int rank = c->rank, size = c->size;
-    const int pof2 = pof2_of(size), rem = size - pof2;
-    const size_t nb = count * ext;
-    int newrank;
-    if (rank < 2 * rem) {                                                   // :110-134
-        if (rank % 2) {
-            TRY(exchange(c, {snd(rank - 1, acc, nb)}, s));
-            newrank = -1;
-        } else {
-            TRY(exchange(c, {rcv(rank + 1, tmp, nb)}, s));
-            TRY(combine(c, tmp, acc, (MPIX_Aint) count, dt, op, s));
-            newrank = rank / 2;
-        }
-    } else {
-        newrank = rank - rem;
-    }
-    std::vector<size_t> cnts(pof2, count / pof2), disps(pof2, 0);
-    for (size_t i = 0; i < count % (size_t) pof2; ++i)
-        cnts[i] += 1;
-    for (int i = 1; i < pof2; ++i)
-        disps[i] = disps[i - 1] + cnts[i - 1];
-    auto sum = [&](int lo, int hi) {
-        size_t t = 0;
-        for (int i = lo; i < hi; ++i)
-            t += cnts[i];
-        return t;
-    };
-    int send_idx = 0, recv_idx = 0, last_idx = 0;
-    if (newrank != -1) {                                                    // :150-210
-        last_idx = pof2;
-        for (int mask = 1; mask < pof2;) {
-            int newdst = newrank ^ mask;
-            int dst = newdst < rem ? newdst * 2 : newdst + rem;
-            size_t send_cnt, recv_cnt;
-            if (newrank < newdst) {
-                send_idx = recv_idx + pof2 / (mask * 2);
-                send_cnt = sum(send_idx, last_idx);
-                recv_cnt = sum(recv_idx, send_idx);
-            } else {
-                recv_idx = send_idx + pof2 / (mask * 2);
-                send_cnt = sum(send_idx, recv_idx);
-                recv_cnt = sum(recv_idx, last_idx);
-            }
-            TRY(exchange(c, {snd(dst, acc + disps[send_idx] * ext, send_cnt * ext),
-                             rcv(dst, tmp + disps[recv_idx] * ext, recv_cnt * ext)}, s));
-            TRY(combine(c, tmp + disps[recv_idx] * ext, acc + disps[recv_idx] * ext,
-                        (MPIX_Aint) recv_cnt, dt, op, s));
-            send_idx = recv_idx;
-            mask <<= 1;
-            if (mask < pof2)
-                last_idx = recv_idx + pof2 / mask;
-        }
+    const int rank = c->rank;
+    const Fold f(rank, c->size, false);
+    const int pof2 = f.pof2, rem = f.rem;
+    int newrank = f.newrank;
+    TRY(fold_in(c, f, acc, tmp, count, dt, op, s, ext));                    // :110-134
+    const Blocks b = Blocks::even(count, pof2);
+    Window win{0, pof2};
+    for (int mask = 1; newrank != -1 && mask < pof2; mask <<= 1) {          // :150-210
+        const int newdst = newrank ^ mask, dst = f.real(newdst);
+        const Step st = halve(&win, newrank < newdst);
+        const size_t roff = b.disps[st.recv_lo] * ext;
+        const size_t recv_cnt = b.range(st.recv_lo, st.recv_hi);
+        TRY(exchange(c, {snd(dst, acc + b.disps[st.send_lo] * ext,
+                             b.range(st.send_lo, st.send_hi) * ext),
+                         rcv(dst, tmp + roff, recv_cnt * ext)}, s));
+        TRY(combine(c, tmp + roff, acc + roff, (MPIX_Aint) recv_cnt, dt, op, s));
     }
     int newroot;                                                            // :215-250
-    if (root < 2 * rem) {
-        if (root % 2) {
-            if (rank == root) {
-                TRY(exchange(c, {rcv(0, acc, cnts[0] * ext)}, s));
-                newrank = 0;
-                send_idx = 0;
-                last_idx = 2;
-            } else if (newrank == 0) {
-                TRY(exchange(c, {snd(root, acc, cnts[0] * ext)}, s));
-                newrank = -1;
-            }
-            newroot = 0;
-        } else {
-            newroot = root / 2;
+    const bool odd_root = root < 2 * rem && root % 2;   // excluded: takes newrank 0's place
+    if (odd_root) {
+        if (rank == root) {
+            TRY(exchange(c, {rcv(0, acc, b.cnt(0) * ext)}, s));
+            newrank = 0;
+            win = Window{0, 1};
+        } else if (newrank == 0) {
+            TRY(exchange(c, {snd(root, acc, b.cnt(0) * ext)}, s));
+            newrank = -1;
         }
+        newroot = 0;
     } else {
-        newroot = root - rem;
+        newroot = root < 2 * rem ? root / 2 : root - rem;
     }
     if (newrank != -1) {                                                    // :252-318
-        int j = 0, mask = 1;
-        while (mask < pof2) {
-            mask <<= 1;
-            ++j;
-        }
-        mask >>= 1;
-        --j;
-        while (mask > 0) {
-            int newdst = newrank ^ mask;
-            int dst = newdst < rem ? newdst * 2 : newdst + rem;
-            if (newdst == 0 && root < 2 * rem && root % 2)
-                dst = root;
-            const int newdst_tree_root = (newdst >> j) << j;
-            const int newroot_tree_root = (newroot >> j) << j;
-            size_t send_cnt, recv_cnt;
-            if (newrank < newdst) {
-                if (mask != pof2 / 2)
-                    last_idx = last_idx + pof2 / (mask * 2);
-                recv_idx = send_idx + pof2 / (mask * 2);
-                send_cnt = sum(send_idx, recv_idx);
-                recv_cnt = sum(recv_idx, last_idx);
-            } else {
-                recv_idx = send_idx - pof2 / (mask * 2);
-                send_cnt = sum(send_idx, last_idx);
-                recv_cnt = sum(recv_idx, send_idx);
-            }
-            if (newdst_tree_root == newroot_tree_root) {
-                TRY(exchange(c, {snd(dst, acc + disps[send_idx] * ext, send_cnt * ext)}, s));
+        for (int mask = pof2 >> 1; mask > 0; mask >>= 1) {
+            const int newdst = newrank ^ mask;
+            const int dst = newdst == 0 && odd_root ? root : f.real(newdst);
+            const Step st = regrow(&win, newrank < newdst);
+            if ((newdst & -mask) == (newroot & -mask)) {    // the partner's subtree has the root
+                TRY(exchange(c, {snd(dst, acc + b.disps[st.send_lo] * ext,
+                                     b.range(st.send_lo, st.send_hi) * ext)}, s));
                 break;
             }
-            TRY(exchange(c, {rcv(dst, acc + disps[recv_idx] * ext, recv_cnt * ext)}, s));
-            if (newrank > newdst)
-                send_idx = recv_idx;
-            mask >>= 1;
-            --j;
+            TRY(exchange(c, {rcv(dst, acc + b.disps[st.recv_lo] * ext,
+                                 b.range(st.recv_lo, st.recv_hi) * ext)}, s));
         }
     }
     return MPIX_REDOP_SUCCESS;
@@ -2245,37 +1890,25 @@ int allreduce_ring(char *rb, size_t count, MPIX_Datatype dt, MPIX_Op op, MPIX_Co
                    hipStream_t s, size_t ext)
 {
     const int rank = c->rank, size = c->size;
-    std::vector<size_t> cnts(size, 0), displs(size, 0);
-    size_t total = 0;
-    for (int i = 0; i < size; ++i) {                                        // :34-42
-        cnts[i] = (count + size - 1) / size;
-        if (total + cnts[i] > count) {
-            cnts[i] = count - total;
-            break;
-        }
-        total += cnts[i];
-    }
-    for (int i = 1; i < size; ++i)
-        displs[i] = displs[i - 1] + cnts[i - 1];
+    const Blocks b = Blocks::ring(count, size);                             // :34-42
+    const std::vector<size_t> &displs = b.disps;
     const int src = (size + rank - 1) % size, dst = (rank + 1) % size;
     for (int i = 0; i < size - 1; ++i) {                                    // :57-76
         const int recv_rank = (size + rank - 2 - i) % size;
         const int send_rank = (size + rank - 1 - i) % size;
-        TRY(exchange(c, {rcv(src, tmp, cnts[recv_rank] * ext),
-                         snd(dst, rb + displs[send_rank] * ext, cnts[send_rank] * ext)}, s));
-        TRY(combine(c, tmp, rb + displs[recv_rank] * ext, (MPIX_Aint) cnts[recv_rank], dt, op,
+        TRY(exchange(c, {rcv(src, tmp, b.cnt(recv_rank) * ext),
+                         snd(dst, rb + displs[send_rank] * ext, b.cnt(send_rank) * ext)}, s));
+        TRY(combine(c, tmp, rb + displs[recv_rank] * ext, (MPIX_Aint) b.cnt(recv_rank), dt, op,
                     s));
     }
     // after step P-2 rank r has folded block r - P = r: that is its finished
     // block, the one MPIR_Allgatherv_intra_ring then circulates (:79-81)
-    const int mine = rank;
     std::vector<MPIX_P2p_op> ops;
     for (int q = 0; q < size; ++q) {
         if (q == rank)
             continue;
-        const int theirs = q;
-        ops.push_back(snd(q, rb + displs[mine] * ext, cnts[mine] * ext));
-        ops.push_back(rcv(q, rb + displs[theirs] * ext, cnts[theirs] * ext));
+        ops.push_back(snd(q, rb + displs[rank] * ext, b.cnt(rank) * ext));
+        ops.push_back(rcv(q, rb + displs[q] * ext, b.cnt(q) * ext));
     }
     return exchange(c, ops, s);
 }
@@ -2317,10 +1950,9 @@ int rs_entry(const void *sendbuf, void *recvbuf, const std::vector<size_t> &cnts
         return finish(c, rs_pull(sb, rb, cnts, dt, op, c, s, ext,
                                  algo == MPIX_RSB_RECURSIVE_HALVING_PULL),
                       s, blocking);
-    int rc = algo == MPIX_RSB_RECURSIVE_HALVING
-                 ? rs_recursive_halving(sb, rb, cnts, dt, op, c, w, s, ext)
-             : algo == MPIX_RSB_RECURSIVE_HALVING_MULTIPATH
-                 ? rs_recursive_halving_multipath(sb, rb, cnts, dt, op, c, w, s, ext)
+    int rc = algo == MPIX_RSB_RECURSIVE_HALVING || algo == MPIX_RSB_RECURSIVE_HALVING_MULTIPATH
+                 ? rs_recursive_halving(sb, rb, cnts, dt, op, c, w, s, ext,
+                                        algo == MPIX_RSB_RECURSIVE_HALVING_MULTIPATH)
                  : algo == MPIX_RSB_PAIRWISE_PIPELINED
                        ? rs_pairwise_pipelined(sb, rb, cnts, dt, op, c, w, s, ext)
                        : rs_pairwise(sb, rb, cnts, dt, op, c, w, s, ext, algo == MPIX_RSB_PAIRWISE);

@@ -36,6 +36,8 @@ $(OUT)/%.o: %.cpp ../../include/mpix_redop.h ../../include/mpix_coll.h redop_dis
 	@mkdir -p $(OUT)
 	$(CXX) $(HOSTFLAGS) $(SANFLAGS) -c $< -o $@
 
+$(OUT)/coll_capi.o: coll_sched.h
+
 $(OUT)/libmpix_redop.so: $(OUT)/redop_capi.o $(KOBJS)
 	$(CXX) -shared -fPIC $(SANFLAGS) -o $@ $^ -L/opt/rocm/lib -lamdhip64 \
 	    -Wl,-soname,libmpix_redop.so -Wl,-rpath,/opt/rocm/lib

@@ -6,43 +6,12 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#include "redop_launch.h"
+
 namespace mpix {
 
-// Runtime parameters some combiners need (Fortran .TRUE./.FALSE.,
-// src/include/mpii_fortlogical.h:15,28), and the completion word of a
-// synchronous call: when `done` is set, the contiguous launcher guarantees
-// that done_seq is stored to it once the combine is complete and visible to
-// the host -- by the kernel itself when it runs as at most kSignalMaxGrid
-// workgroups (the last one to finish, counted on done_ctr, stores it: no
-// end-of-kernel + stream-packet round trip), else by a stream write after it.
-struct Params {
-    long long ftrue;
-    long long ffalse;
-    uint32_t *done = nullptr;       // pinned, fine-grained host word
-    uint32_t *done_ctr = nullptr;   // device word, 0 between launches
-    uint32_t done_seq = 0;
-    // blocks from this index on store write-through (sc0 sc1: the line leaves
-    // the XCD's L2 at once instead of staying dirty until the end-of-kernel
-    // write-back); 0xffffffff = none (LaunchCfg::wt_tail)
-    uint32_t wt_from = 0xffffffffu;
-    uint32_t wt_every = 0;      // and blocks b with b % wt_every == wt_phase (0 = none)
-    uint32_t wt_phase = 0;
-    uint32_t wt_xcd = 0;        // and every block running on an XCD whose bit is set
-    // split combiners (is_split, redop_kernels.h): one 64-bit word per 64
-    // units, bit j set when unit 64 w + j left its fast path (fixup_acquire)
-    uint64_t *fixup = nullptr;
-};
-
+// Params, LaunchCfg, grid_for and max_blocks: redop_launch.h
 constexpr unsigned kSignalMaxGrid = 64;     // 64 tiles of 64 x 1 packets: 64 KiB per operand
-
-struct LaunchCfg {
-    int block;          // threads per block (multiple of 64)
-    int max_grid;       // 0 = no cap (one tile per block)
-    int wt_tail;        // contiguous kernel: the last wt_tail blocks store write-through
-    int wt_every;       // ... and blocks b with b % wt_every == wt_phase
-    int wt_phase;
-    int wt_xcd;         // ... and blocks on the XCDs (HW_REG_XCC_ID) of this bit mask
-};
 
 // One (op, type) pair: launchers for the contiguous and the vector-target form.
 struct Entry {
@@ -60,27 +29,6 @@ struct Entry {
     hipError_t (*batch)(const void *const *ins, void *const *ios, const uint64_t *counts, int k,
                         const Params &, const LaunchCfg &, hipStream_t);
 };
-
-// Most blocks one dispatch of `block`-thread workgroups may have: HIP caps a
-// dispatch at UINT32_MAX work-items (gridDim.x * blockDim.x), so with one-wave
-// blocks that is 2^26 - 1 blocks, not 2^31.  Every kernel
-// launched through grid_for strides over the rest.
-constexpr uint64_t max_blocks(uint64_t block)
-{
-    return 0xffffffffull / (block ? block : 1);
-}
-
-inline unsigned grid_for(uint64_t work_per_block_units, uint64_t n, int max_grid, uint64_t block)
-{
-    uint64_t g = (n + work_per_block_units - 1) / work_per_block_units;
-    if (g == 0)
-        g = 1;
-    if (max_grid > 0 && g > (uint64_t) max_grid)
-        g = (uint64_t) max_grid;
-    if (g > max_blocks(block))
-        g = max_blocks(block);
-    return (unsigned) g;
-}
 
 constexpr int kMaxBatchSegs = 64;       // MPIX_BATCH_MAX
 

@@ -1041,37 +1041,46 @@ k_iov(const typename C::unit *__restrict__ in, typename C::unit *__restrict__ io
     }
 }
 
-// The store policy (LaunchCfg::wt_*) of a launch of `grid` blocks.
-inline void set_store_policy(Params &p, const LaunchCfg &cfg, unsigned grid)
-{
-    if (cfg.wt_tail > 0)
-        p.wt_from = grid > (unsigned) cfg.wt_tail ? grid - (unsigned) cfg.wt_tail : 0u;
-    p.wt_every = cfg.wt_every > 0 ? (unsigned) cfg.wt_every : 0u;
-    p.wt_phase = (unsigned) cfg.wt_phase;
-    p.wt_xcd = (unsigned) cfg.wt_xcd & 0xffu;
-}
+// ---------------------------------------------------------------------------
+// The launchers: each asks redop_launch.h for its plan (the form, the grid and
+// block, the split), switches on the form and launches.  The rules, and the
+// bug reports behind them, are at the plan functions.
 
-// k_contig32's block (its __launch_bounds__)
-// One-wave blocks for the stride-2 vector target and the 32-byte units too
+// One-wave blocks for the stride-2 vector target (plan_vector) and the 32-byte
+// units (plan_contig's Packets32) too
 // (round 5, tools/gpu_u_ab.sh against 256 threads, profiles/r05_block64_vec32.json):
 // config 5 0.449 -> 0.433 ms; LONG_DOUBLE_INT MINLOC / MAXLOC 6.74-6.78 ->
 // 7.06-7.09 TB/s, the complex long double / binary128 rows even to +2 %
 #ifndef MPIX_REDOP_VBLOCK
 #define MPIX_REDOP_VBLOCK 64        // the stride-2 vector target's block
 #endif
+// k_contig32's block (its __launch_bounds__)
 constexpr unsigned kContig32Block = MPIX_REDOP_BLOCK32;
 
+// LDS per 64 threads of a multi-input fold block (plan_multi): 160 KiB per CU
+// / 6656 B = 24 one-wave blocks = 6 waves per SIMD (the kernel itself uses no
+// LDS)
+constexpr unsigned kMultiLds = 6656;
+
+// what this unit's launchers of combiner C were compiled with
+template <class C> constexpr LaunchFacts launch_facts()
+{
+    return LaunchFacts{is_split<C>::value, MPIX_REDOP_UNROLL,  MPIX_REDOP_UNROLL32,
+                       MPIX_REDOP_BLOCK32, MPIX_REDOP_VBLOCK, kSignalMaxGrid,
+                       kMultiLds};
+}
+
+inline uintptr_t addr(const void *p) { return reinterpret_cast<uintptr_t>(p); }
+
 // k_contig32 over 16-byte-aligned 32-byte units (`io` read in the inout
-// role, the result to `out`: io itself, or the tree's output); a split
-// combiner adds its fixup launch
+// role, the result to `out`: io itself, or the tree's output) on the plan's
+// grid; a split combiner adds its fixup launch
 template <class C>
 hipError_t launch_contig32(const typename C::unit *in, const typename C::unit *io,
-                           typename C::unit *out, uint64_t count, const Params &prm,
+                           typename C::unit *out, uint64_t count, unsigned grid, const Params &prm,
                            const LaunchCfg &cfg, hipStream_t s)
 {
     constexpr int U32 = MPIX_REDOP_UNROLL32;
-    const unsigned grid = grid_for((uint64_t) kContig32Block * U32, count, cfg.max_grid,
-                                   kContig32Block);
     Params p = prm;
     p.done = nullptr;
     set_store_policy(p, cfg, grid);
@@ -1098,122 +1107,96 @@ hipError_t launch_contig32(const typename C::unit *in, const typename C::unit *i
     return e;
 }
 
-// Contiguous launcher: chooses the packet or the element-wise kernel.
+// The launch of a plan_contig plan (launch_vector's too, for bl == st)
 template <class C>
-hipError_t launch_contig(const void *in, void *io, uint64_t count, const Params &prm,
-                         const LaunchCfg &cfg, hipStream_t s)
+hipError_t run_contig(const LaunchPlan &pl, const void *in, void *io, uint64_t count,
+                      const Params &prm, const LaunchCfg &cfg, hipStream_t s)
 {
     using T = typename C::unit;
-    constexpr uint64_t E = sizeof(T) <= 16 ? 16 / sizeof(T) : 1;
     const T *tin = static_cast<const T *>(in);
     T *tio = static_cast<T *>(io);
-    bool signalled = false;
-    uintptr_t ai = reinterpret_cast<uintptr_t>(in), ao = reinterpret_cast<uintptr_t>(io);
-    if constexpr (sizeof(T) > 16) {
-        // 32-byte units (the long double / binary128 pairs and complex): two
-        // units of two 16-byte packets per lane and operand, as many bytes in
-        // flight as k_contig's four packets; operands off the 16-byte grid go
-        // element-wise
-        if (((ai | ao) & 15) == 0) {
-            hipError_t e = launch_contig32<C>(tin, tio, tio, count, prm, cfg, s);
-            if (e != hipSuccess)
-                return e;
-        } else {
-            unsigned grid = grid_for((uint64_t) cfg.block * 4, count, cfg.max_grid, cfg.block);
-            hipLaunchKernelGGL((k_elem<C>), dim3(grid), dim3(cfg.block), 0, s, tin, tio, count,
-                               prm, grid, (uint32_t) cfg.block);
-        }
-    } else if ((ao % sizeof(T)) == 0 && (ai % sizeof(T)) == 0) {
-        uint64_t head = ((16 - (ao & 15)) & 15) / sizeof(T);
-        if (head > count)
-            head = count;
-        uint64_t npk = (count - head) / E;
-        uint64_t tail_start = head + npk * E;
-        uint32_t ntail = (uint32_t) (count - tail_start);
-        const uint64_t tile = (uint64_t) cfg.block * MPIX_REDOP_UNROLL;
-        unsigned grid = grid_for(tile, npk, cfg.max_grid, cfg.block);
-        // up to kSignalMaxGrid workgroups (64 KiB per operand at the defaults): the
-        // kernel stores the completion word itself (Params::done)
-        Params p = prm;
-        if (grid > (prm.done_ctr ? kSignalMaxGrid : 1u))
-            p.done = nullptr;
-        set_store_policy(p, cfg, grid);
-        signalled = p.done != nullptr;
-        if ((ai & 15) == (ao & 15))
-            hipLaunchKernelGGL(
-                (k_contig<C, MPIX_REDOP_UNROLL, MPIX_REDOP_NT_LOAD, MPIX_REDOP_NT_STORE, true>),
-                dim3(grid), dim3(cfg.block), 0, s, tin, tio, head, npk, tail_start, ntail, p,
-                grid, (uint32_t) cfg.block);
-        else
-            hipLaunchKernelGGL(
-                (k_contig<C, MPIX_REDOP_UNROLL, MPIX_REDOP_NT_LOAD, MPIX_REDOP_NT_STORE, false>),
-                dim3(grid), dim3(cfg.block), 0, s, tin, tio, head, npk, tail_start, ntail, p,
-                grid, (uint32_t) cfg.block);
-    } else {
-        unsigned grid = grid_for((uint64_t) cfg.block * 4, count, cfg.max_grid, cfg.block);
-        hipLaunchKernelGGL((k_elem<C>), dim3(grid), dim3(cfg.block), 0, s, tin, tio, count, prm,
-                           grid, (uint32_t) cfg.block);
+    const PacketSplit &sp = pl.split;
+    switch (pl.form) {
+        case Form::Packets32:
+            if constexpr (sizeof(T) > 16) {
+                hipError_t e = launch_contig32<C>(tin, tio, tio, count, pl.grid, prm, cfg, s);
+                if (e != hipSuccess)
+                    return e;
+            }
+            break;
+        case Form::PacketsAin:
+        case Form::PacketsUin:
+            if constexpr (sizeof(T) <= 16) {
+                Params p = prm;
+                if (!pl.signals)
+                    p.done = nullptr;
+                set_store_policy(p, cfg, pl.grid);
+                if (pl.form == Form::PacketsAin)
+                    hipLaunchKernelGGL(
+                        (k_contig<C, MPIX_REDOP_UNROLL, MPIX_REDOP_NT_LOAD, MPIX_REDOP_NT_STORE, true>),
+                        dim3(pl.grid), dim3(pl.block), 0, s, tin, tio, sp.head, sp.npk,
+                        sp.tail_start, sp.ntail, p, pl.grid, pl.block);
+                else
+                    hipLaunchKernelGGL(
+                        (k_contig<C, MPIX_REDOP_UNROLL, MPIX_REDOP_NT_LOAD, MPIX_REDOP_NT_STORE, false>),
+                        dim3(pl.grid), dim3(pl.block), 0, s, tin, tio, sp.head, sp.npk,
+                        sp.tail_start, sp.ntail, p, pl.grid, pl.block);
+            }
+            break;
+        default:
+            hipLaunchKernelGGL((k_elem<C>), dim3(pl.grid), dim3(pl.block), 0, s, tin, tio, count, prm,
+                               pl.grid, pl.block);
     }
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess && prm.done && !signalled)
+    if (e == hipSuccess && prm.done && !pl.signals)
         e = hipStreamWriteValue32(s, (void *) prm.done, prm.done_seq, 0);
     return e;
 }
 
-// LDS per 64 threads of a multi-input fold block: 160 KiB per CU / 6656 B =
-// 24 one-wave blocks = 6 waves per SIMD (the kernel itself uses no LDS)
-constexpr unsigned kMultiLds = 6656;
+// Contiguous launcher: the packet, the 32-byte packet or the element-wise kernel.
+template <class C>
+hipError_t launch_contig(const void *in, void *io, uint64_t count, const Params &prm,
+                         const LaunchCfg &cfg, hipStream_t s)
+{
+    const LaunchPlan pl = plan_contig(addr(in), addr(io), sizeof(typename C::unit), count, cfg,
+                                      launch_facts<C>(), prm.done, prm.done_ctr);
+    return run_contig<C>(pl, in, io, count, prm, cfg, s);
+}
 
 template <class C>
 hipError_t launch_multi(const void *const *ins, int k, void *io, uint64_t count, const Params &prm,
                         const LaunchCfg &cfg, hipStream_t s)
 {
     using T = typename C::unit;
-    constexpr uint64_t E = sizeof(T) <= 16 ? 16 / sizeof(T) : 1;
     MultiIn<T> mi{};
-    uintptr_t ao = reinterpret_cast<uintptr_t>(io);
-    bool aligned = sizeof(T) <= 16 && (ao % sizeof(T)) == 0;
+    uintptr_t ai[kMaxMulti];
     for (int q = 0; q < k; ++q) {
         mi.p[q] = static_cast<const T *>(ins[q]);
-        aligned = aligned && ((reinterpret_cast<uintptr_t>(ins[q]) & 15) == (ao & 15));
+        ai[q] = addr(ins[q]);
     }
     T *tio = static_cast<T *>(io);
-    if constexpr (sizeof(T) > 16)
-        aligned = false;
-    if (aligned) {
-        uint64_t head = ((16 - (ao & 15)) & 15) / sizeof(T);
-        if (head > count)
-            head = count;
-        uint64_t npk = (count - head) / E;
-        uint64_t tail_start = head + npk * E;
-        uint32_t ntail = (uint32_t) (count - tail_start);
+    const LaunchPlan pl = plan_multi(ai, k, addr(io), sizeof(T), count, cfg, launch_facts<C>());
+    if (pl.form == Form::PacketsAin) {
         // one packet per lane per input: 6.16 / 6.20 TB/s at k = 7 (256 MiB /
         // 1 GiB, store policy on) against 6.04 / 5.83 with two; 4 measured no
         // better than 2 (tools/tree8_probe.hip, tools/multi_probe.py)
-        constexpr int U = 1;
-        unsigned grid = grid_for((uint64_t) cfg.block * U, npk, cfg.max_grid, cfg.block);
-        Params p = prm;
-        set_store_policy(p, cfg, grid);
-        // k >= 2 inputs: unused LDS per block caps the waves per SIMD at 6
-        // (24 one-wave blocks per CU): with k + 2 streams per wave fewer
-        // waves in flight run faster -- 256 MiB fp32, one-wave blocks, store
-        // policy on: k = 3 6.53 -> 6.91, k = 7 6.53 -> 6.92, k = 15 6.38 ->
-        // 6.65 TB/s against the round-5 form; the headline kernel (k = 1)
-        // loses with any cap (7.04 -> 6.73) and keeps none
+        // plan_multi's LDS for k >= 2 inputs: unused LDS per block caps the
+        // waves per SIMD at 6 (24 one-wave blocks per CU): with k + 2 streams
+        // per wave fewer waves in flight run faster -- 256 MiB fp32, one-wave
+        // blocks, store policy on: k = 3 6.53 -> 6.91, k = 7 6.53 -> 6.92,
+        // k = 15 6.38 -> 6.65 TB/s against the round-5 form; the headline
+        // kernel (k = 1) loses with any cap (7.04 -> 6.73) and keeps none
         // (profiles/r06_multi_fold_caps2.json)
-        size_t lds = 0;
-        if (k >= 2) {
-            lds = (size_t) kMultiLds * ((unsigned) cfg.block / 64u);
-            if (lds > 65536)
-                lds = 0;
+        if constexpr (sizeof(T) <= 16) {
+            Params p = prm;
+            set_store_policy(p, cfg, pl.grid);
+            hipLaunchKernelGGL((k_contig_multi<C, 1>), dim3(pl.grid), dim3(pl.block), pl.lds, s, mi,
+                               k, tio, pl.split.head, pl.split.npk, pl.split.tail_start,
+                               pl.split.ntail, p, pl.grid, pl.block);
         }
-        if constexpr (sizeof(T) <= 16)
-            hipLaunchKernelGGL((k_contig_multi<C, U>), dim3(grid), dim3(cfg.block), lds, s, mi, k,
-                               tio, head, npk, tail_start, ntail, p, grid, (uint32_t) cfg.block);
     } else {
-        unsigned grid = grid_for((uint64_t) cfg.block * 4, count, cfg.max_grid, cfg.block);
-        hipLaunchKernelGGL((k_elem_multi<C>), dim3(grid), dim3(cfg.block), 0, s, mi, k, tio, count,
-                           prm, grid, (uint32_t) cfg.block);
+        hipLaunchKernelGGL((k_elem_multi<C>), dim3(pl.grid), dim3(pl.block), 0, s, mi, k, tio, count,
+                           prm, pl.grid, pl.block);
     }
     return hipGetLastError();
 }
@@ -1225,85 +1208,63 @@ hipError_t launch_tree(const void *const *ins, int k, void *out, uint64_t count,
                        const LaunchCfg &cfg, hipStream_t s)
 {
     using T = typename C::unit;
-    constexpr uint64_t E = sizeof(T) <= 16 ? 16 / sizeof(T) : 1;
     MultiIn<T> mi{};
-    uintptr_t ao = reinterpret_cast<uintptr_t>(out);
-    bool aligned = sizeof(T) <= 16 && (ao % sizeof(T)) == 0;
-    uint32_t pres = 0;
+    uintptr_t ai[kMaxMulti];
     for (int q = 0; q < k; ++q) {
         mi.p[q] = static_cast<const T *>(ins[q]);
-        if (!ins[q])
-            continue;
-        pres |= 1u << q;
-        aligned = aligned && ((reinterpret_cast<uintptr_t>(ins[q]) & 15) == (ao & 15));
+        ai[q] = addr(ins[q]);
     }
     T *tout = static_cast<T *>(out);
-    if constexpr (sizeof(T) > 16) {
-        // out = slot 0 OP slot 1 on 32-byte units, all three 16-byte aligned:
-        // k_contig32 with slot 0 in the inout role (recursive halving's
-        // combine_to); other shapes go element-wise below.  So does a split
-        // combiner whose output is slot 1: k_contig32 stores the inout role's
-        // value (slot 0's) into every unit it declines, and k_fixup32 would
-        // then read that where it expects slot 1's (out over slot 0 stores
-        // slot 0's value over itself)
-        const bool over_in = is_split<C>::value && out == ins[1];
-        if (k == 2 && pres == 3u && !over_in &&
-            ((ao | reinterpret_cast<uintptr_t>(ins[0]) | reinterpret_cast<uintptr_t>(ins[1])) & 15) ==
-                0) {
-            return launch_contig32<C>(mi.p[1], mi.p[0], tout, count, prm, cfg, s);
-        }
-    }
-    if (aligned) {
-        uint64_t head = ((16 - (ao & 15)) & 15) / sizeof(T);
-        if (head > count)
-            head = count;
-        uint64_t npk = (count - head) / E;
-        uint64_t tail_start = head + npk * E;
-        uint32_t ntail = (uint32_t) (count - tail_start);
-        Params p = prm;
-        // forms by slot count (tools/tree8_probe.hip, profiles/r05_tree_forms.json;
-        // fp32 SUM at 256 MiB / 1 GiB per operand, store policy on):
-        //   k = 2   the fold order, 2 packets per lane     6.81 / 6.94 TB/s
-        //           (all 4 x 2 loads up front: 6.44 / 6.84)
-        //   k = 4   all 4 x 2 loads up front               6.40 / 6.61
-        //           (the fold order, 1 packet: 6.34 / 6.53)
-        //   k = 8   the fold order, 1 packet per lane      6.47 / 6.36
-        //           (8 x 2 up front 5.79 / 5.43, 16 x 1 up front 5.68 / 5.22)
-        //   k = 16  the fold order, 1 packet per lane      6.37 / 5.92
-        //           (16 x 1 up front 5.86 / 5.50)
-        // Loading slots only as the fold reaches them keeps 39 VGPRs live at
-        // k = 8 (8 waves per SIMD) against 111 for the up-front form (4), and
-        // with nine streams the waves, not each wave's bytes in flight, carry
-        // the rate.  The store policy: +5 % at k = 2, +3.8 % at k = 4, neutral
-        // above.
-        // One-wave (64-thread) blocks, as the contiguous kernel: k = 2 / 4 / 8
-        // / 16 at 6.84-6.96 / 6.48-6.61 / 6.58-6.67 / 6.06-6.45 TB/s against
-        // 6.64-6.76 / 6.36-6.43 / 6.25-6.28 / 5.82-6.43 with 256 threads
-        // (r05_tree_forms.json, last run).
-        // The public entry takes k = 2, 4, 8, 16 only (the collectives pad an odd
-        // world's fold with absent slots); a k between them runs the next
-        // larger form, whose uniform branches skip the slots >= k.
-        constexpr unsigned kTreeBlock = 64;
-        const unsigned per = k <= 4 ? kTreeBlock * 2 : kTreeBlock;
-        const unsigned grid = grid_for(per, npk, 0, kTreeBlock);
-        set_store_policy(p, cfg, grid);
-        if constexpr (sizeof(T) <= 16) {
-            if (k <= 2)     // out = a OP b (recursive halving's combine_to)
-                hipLaunchKernelGGL((k_contig_tree_rec<C, 2, 2>), dim3(grid), dim3(kTreeBlock), 0, s,
-                                   mi, k, pres, tout, head, npk, tail_start, ntail, p);
-            else if (k <= 4)
-                hipLaunchKernelGGL((k_contig_tree<C, 4, 2>), dim3(grid), dim3(kTreeBlock), 0, s, mi,
-                                   k, pres, tout, head, npk, tail_start, ntail, p);
-            else if (k <= 8)    // the P = 8 pull's fold
-                hipLaunchKernelGGL((k_contig_tree_rec<C, 8, 1>), dim3(grid), dim3(kTreeBlock), 0, s,
-                                   mi, k, pres, tout, head, npk, tail_start, ntail, p);
-            else
-                hipLaunchKernelGGL((k_contig_tree_rec<C, kMaxMulti, 1>), dim3(grid), dim3(kTreeBlock),
-                                   0, s, mi, k, pres, tout, head, npk, tail_start, ntail, p);
-        }
-    } else {
-        hipLaunchKernelGGL((k_elem_tree<C>), dim3(grid_for(256 * 4, count, 0, 256)), dim3(256), 0, s,
-                           mi, k, pres, tout, count, prm);
+    const LaunchPlan pl = plan_tree(ai, k, addr(out), sizeof(T), count, cfg, launch_facts<C>());
+    const PacketSplit &sp = pl.split;
+    // plan_tree's forms by slot count (tools/tree8_probe.hip,
+    // profiles/r05_tree_forms.json; fp32 SUM at 256 MiB / 1 GiB per operand,
+    // store policy on):
+    //   k = 2   the fold order, 2 packets per lane     6.81 / 6.94 TB/s
+    //           (all 4 x 2 loads up front: 6.44 / 6.84)
+    //   k = 4   all 4 x 2 loads up front               6.40 / 6.61
+    //           (the fold order, 1 packet: 6.34 / 6.53)
+    //   k = 8   the fold order, 1 packet per lane      6.47 / 6.36
+    //           (8 x 2 up front 5.79 / 5.43, 16 x 1 up front 5.68 / 5.22)
+    //   k = 16  the fold order, 1 packet per lane      6.37 / 5.92
+    //           (16 x 1 up front 5.86 / 5.50)
+    // Loading slots only as the fold reaches them keeps 39 VGPRs live at
+    // k = 8 (8 waves per SIMD) against 111 for the up-front form (4), and
+    // with nine streams the waves, not each wave's bytes in flight, carry
+    // the rate.  The store policy: +5 % at k = 2, +3.8 % at k = 4, neutral
+    // above.
+    // One-wave (64-thread) blocks (kTreeBlock), as the contiguous kernel:
+    // k = 2 / 4 / 8 / 16 at 6.84-6.96 / 6.48-6.61 / 6.58-6.67 / 6.06-6.45 TB/s
+    // against 6.64-6.76 / 6.36-6.43 / 6.25-6.28 / 5.82-6.43 with 256 threads
+    // (r05_tree_forms.json, last run).
+    // The public entry takes k = 2, 4, 8, 16 only (the collectives pad an odd
+    // world's fold with absent slots).
+    switch (pl.form) {
+        case Form::TreePair32:
+            if constexpr (sizeof(T) > 16)
+                return launch_contig32<C>(mi.p[1], mi.p[0], tout, count, pl.grid, prm, cfg, s);
+            break;
+        case Form::TreeElem:
+            hipLaunchKernelGGL((k_elem_tree<C>), dim3(pl.grid), dim3(pl.block), 0, s, mi, k, pl.pres,
+                               tout, count, prm);
+            break;
+        default:
+            if constexpr (sizeof(T) <= 16) {
+                Params p = prm;
+                set_store_policy(p, cfg, pl.grid);
+                auto launch = [&](auto kernel) {
+                    hipLaunchKernelGGL(kernel, dim3(pl.grid), dim3(pl.block), 0, s, mi, k, pl.pres,
+                                       tout, sp.head, sp.npk, sp.tail_start, sp.ntail, p);
+                };
+                if (pl.form == Form::Tree2x2)   // out = a OP b (recursive halving's combine_to)
+                    launch(k_contig_tree_rec<C, 2, 2>);
+                else if (pl.form == Form::Tree4x2)
+                    launch(k_contig_tree<C, 4, 2>);
+                else if (pl.form == Form::Tree8x1)      // the P = 8 pull's fold
+                    launch(k_contig_tree_rec<C, 8, 1>);
+                else
+                    launch(k_contig_tree_rec<C, kMaxMulti, 1>);
+            }
     }
     return hipGetLastError();
 }
@@ -1313,30 +1274,30 @@ hipError_t launch_vector(const void *in, void *io, uint64_t count, uint64_t bl, 
                          const Params &prm, const LaunchCfg &cfg, hipStream_t s)
 {
     using T = typename C::unit;
-    uint64_t n = count * bl;
+    const uint64_t n = count * bl;
     if (n == 0)
         return hipSuccess;
-    if (bl == st)       // contiguous after all
-        return launch_contig<C>(in, io, n, prm, cfg, s);
-    unsigned grid = grid_for((uint64_t) cfg.block * 4, n, cfg.max_grid, cfg.block);
-    bool s2 = false;
-    if constexpr (sizeof(T) <= 16)
-        s2 = bl == 1 && st == 2 && (reinterpret_cast<uintptr_t>(io) % (2 * sizeof(T))) == 0;
-    if (s2) {
-        if constexpr (sizeof(T) <= 16) {
-            constexpr unsigned kVb = MPIX_REDOP_VBLOCK;
-            const unsigned g2 = grid_for(kVb, n, cfg.max_grid, kVb);
-            hipLaunchKernelGGL((k_vector_s2<C>), dim3(g2), dim3(kVb), 0, s,
-                               static_cast<const T *>(in), static_cast<T *>(io), n, prm, g2, kVb);
-        }
-    } else if (bl == 1)
-        hipLaunchKernelGGL((k_vector1<C>), dim3(grid), dim3(cfg.block), 0, s,
-                           static_cast<const T *>(in), static_cast<T *>(io), n, st, prm, grid,
-                           (uint32_t) cfg.block);
-    else
-        hipLaunchKernelGGL((k_vector<C>), dim3(grid), dim3(cfg.block), 0, s,
-                           static_cast<const T *>(in), static_cast<T *>(io), n, bl, st, prm, grid,
-                           (uint32_t) cfg.block);
+    const LaunchPlan pl = plan_vector(addr(in), addr(io), sizeof(T), n, bl, st, cfg,
+                                      launch_facts<C>(), prm.done, prm.done_ctr);
+    const T *tin = static_cast<const T *>(in);
+    T *tio = static_cast<T *>(io);
+    switch (pl.form) {
+        case Form::VectorS2:
+            if constexpr (sizeof(T) <= 16)
+                hipLaunchKernelGGL((k_vector_s2<C>), dim3(pl.grid), dim3(pl.block), 0, s, tin, tio, n,
+                                   prm, pl.grid, pl.block);
+            break;
+        case Form::Vector1:
+            hipLaunchKernelGGL((k_vector1<C>), dim3(pl.grid), dim3(pl.block), 0, s, tin, tio, n, st,
+                               prm, pl.grid, pl.block);
+            break;
+        case Form::Vector:
+            hipLaunchKernelGGL((k_vector<C>), dim3(pl.grid), dim3(pl.block), 0, s, tin, tio, n, bl, st,
+                               prm, pl.grid, pl.block);
+            break;
+        default:        // bl == st: contiguous after all
+            return run_contig<C>(pl, in, io, n, prm, cfg, s);
+    }
     return hipGetLastError();
 }
 
@@ -1387,122 +1348,47 @@ hipError_t launch_batch(const void *const *ins, void *const *ios, const uint64_t
     using T = typename C::unit;
     Params p = prm;
     p.done = nullptr;
-    if constexpr (is_split<C>::value) {
-        // a split combiner: each triple its own launches (launch_contig: the
-        // fast kernel and its fixup)
-        for (int i = 0; i < k; ++i)
-            if (counts[i]) {
-                hipError_t e = launch_contig<C>(ins[i], ios[i], counts[i], p, cfg, s);
-                if (e != hipSuccess)
-                    return e;
-            }
-        return hipSuccess;
-    } else if constexpr (sizeof(T) > 16) {
-        // 32-byte units: the 16-byte-aligned triples as one k_batch32 launch,
-        // the others element-wise one launch each
-        constexpr int U32 = MPIX_REDOP_UNROLL32;
-        const uint64_t tile = (uint64_t) kContig32Block * U32;
-        BatchTab tab;
-        int n = 0;
-        uint64_t blocks = 0;
-        auto flush = [&]() -> hipError_t {
-            if (!n)
-                return hipSuccess;
-            Params q = p;
-            set_store_policy(q, cfg, (unsigned) blocks);
-            hipLaunchKernelGGL((k_batch32<C, U32, MPIX_REDOP_NT_LOAD, MPIX_REDOP_NT_STORE>),
-                               dim3((unsigned) blocks), dim3(kContig32Block), 0, s, tab, n, q,
-                               kContig32Block);
-            n = 0;
-            blocks = 0;
-            return hipGetLastError();
-        };
-        for (int i = 0; i < k; ++i) {
-            const uint64_t count = counts[i];
-            if (!count)
-                continue;
-            if (((reinterpret_cast<uintptr_t>(ins[i]) | reinterpret_cast<uintptr_t>(ios[i])) & 15) !=
-                0) {
-                hipError_t e = launch_contig<C>(ins[i], ios[i], count, p, cfg, s);
-                if (e != hipSuccess)
-                    return e;
-                continue;
-            }
-            const uint64_t nb = (count + tile - 1) / tile;
-            if (nb > max_blocks(kContig32Block)) {   // more tiles than one grid holds: a call of its own
-                hipError_t e = launch_contig<C>(ins[i], ios[i], count, p, cfg, s);
-                if (e != hipSuccess)
-                    return e;
-                continue;
-            }
-            if (blocks + nb > max_blocks(kContig32Block)) {
-                hipError_t e = flush();
-                if (e != hipSuccess)
-                    return e;
-            }
-            tab.blk0[n] = (uint32_t) blocks;
-            tab.s[n] = BatchSeg{ins[i], ios[i], count, 0, 0, 1, {0, 0, 0, 0, 0}};
-            blocks += nb;
-            ++n;
-        }
-        return flush();
-    } else {
-        constexpr uint64_t E = 16 / sizeof(T);
-        const uint64_t tile = (uint64_t) cfg.block * MPIX_REDOP_UNROLL;
-        BatchTab tab;
-        int n = 0;
-        uint64_t blocks = 0;
-        auto flush = [&]() -> hipError_t {
-            if (!n)
-                return hipSuccess;
-            Params q = p;
-            set_store_policy(q, cfg, (unsigned) blocks);
-            hipLaunchKernelGGL((k_batch<C, MPIX_REDOP_UNROLL, MPIX_REDOP_NT_LOAD, MPIX_REDOP_NT_STORE>),
-                               dim3((unsigned) blocks), dim3(cfg.block), 0, s, tab, n, q,
-                               (uint32_t) blocks, (uint32_t) cfg.block);
-            n = 0;
-            blocks = 0;
-            return hipGetLastError();
-        };
-        for (int i = 0; i < k; ++i) {
-            const uint64_t count = counts[i];
-            if (!count)
-                continue;
-            const uintptr_t ai = reinterpret_cast<uintptr_t>(ins[i]);
-            const uintptr_t ao = reinterpret_cast<uintptr_t>(ios[i]);
-            if ((ai % sizeof(T)) || (ao % sizeof(T))) {
-                hipError_t e = launch_contig<C>(ins[i], ios[i], count, p, cfg, s);
-                if (e != hipSuccess)
-                    return e;
-                continue;
-            }
-            uint64_t head = ((16 - (ao & 15)) & 15) / sizeof(T);
-            if (head > count)
-                head = count;
-            const uint64_t npk = (count - head) / E;
-            const uint64_t ntail = count - head - npk * E;
-            uint64_t nb = (npk + tile - 1) / tile;
-            if (nb == 0)
-                nb = 1;         // a segment of head / tail elements only
-            if (nb > max_blocks(cfg.block)) {    // more tiles than one grid holds: launch_contig
-                hipError_t e = launch_contig<C>(ins[i], ios[i], count, p, cfg, s);   // loops
-                if (e != hipSuccess)
-                    return e;
-                continue;
-            }
-            if (blocks + nb > max_blocks(cfg.block)) {
-                hipError_t e = flush();
-                if (e != hipSuccess)
-                    return e;
-            }
-            tab.blk0[n] = (uint32_t) blocks;
-            tab.s[n] = BatchSeg{ins[i], ios[i], npk, (uint8_t) head, (uint8_t) ntail,
-                                (uint8_t) ((ai & 15) == (ao & 15)), {0, 0, 0, 0, 0}};
-            blocks += nb;
-            ++n;
-        }
-        return flush();
+    uintptr_t ai[kMaxBatch], ao[kMaxBatch];
+    for (int i = 0; i < k; ++i) {
+        ai[i] = addr(ins[i]);
+        ao[i] = addr(ios[i]);
     }
+    BatchPacker pack(ai, ao, counts, k, sizeof(T), cfg, launch_facts<C>());
+    BatchTab tab;
+    for (BatchStep st; pack.next(st);) {
+        hipError_t e = hipSuccess;
+        switch (st.kind) {
+            case BatchStep::Own:    // launch_contig (a split combiner: with its fixup)
+                e = launch_contig<C>(ins[st.i], ios[st.i], counts[st.i], p, cfg, s);
+                break;
+            case BatchStep::Seg:
+                tab.blk0[st.n] = st.blk0;
+                tab.s[st.n] = BatchSeg{ins[st.i], ios[st.i], st.split.npk, (uint8_t) st.split.head,
+                                       (uint8_t) st.split.ntail, (uint8_t) st.ain, {0, 0, 0, 0, 0}};
+                break;
+            case BatchStep::Flush: {
+                Params q = p;
+                const unsigned grid = (unsigned) st.blocks;
+                set_store_policy(q, cfg, grid);
+                if constexpr (is_split<C>::value)
+                    ;   // every segment a call of its own
+                else if constexpr (sizeof(T) > 16)
+                    hipLaunchKernelGGL((k_batch32<C, MPIX_REDOP_UNROLL32, MPIX_REDOP_NT_LOAD,
+                                                  MPIX_REDOP_NT_STORE>),
+                                       dim3(grid), dim3(pack.block()), 0, s, tab, st.n, q,
+                                       pack.block());
+                else
+                    hipLaunchKernelGGL((k_batch<C, MPIX_REDOP_UNROLL, MPIX_REDOP_NT_LOAD,
+                                                MPIX_REDOP_NT_STORE>),
+                                       dim3(grid), dim3(pack.block()), 0, s, tab, st.n, q, grid,
+                                       pack.block());
+                e = hipGetLastError();
+            }
+        }
+        if (e != hipSuccess)
+            return e;
+    }
+    return hipSuccess;
 }
 
 // ---------------------------------------------------------------------------
@@ -1657,38 +1543,24 @@ hipError_t launch_getacc(const void *in, void *res, void *io, uint64_t count, co
     using T = typename C::unit;
     const T *tin = static_cast<const T *>(in);
     T *tres = static_cast<T *>(res), *tio = static_cast<T *>(io);
-    const uintptr_t ai = reinterpret_cast<uintptr_t>(in), ar = reinterpret_cast<uintptr_t>(res),
-                    ao = reinterpret_cast<uintptr_t>(io);
     Params p = prm;
     p.done = nullptr;       // the fetch entries wait on the stream
     p.fixup = nullptr;
-    bool packets = false;
-    if constexpr (sizeof(T) <= 16)
-        packets = (ai % sizeof(T)) == 0 && (ar % sizeof(T)) == 0 && (ao % sizeof(T)) == 0;
-    if (packets) {
-        if constexpr (sizeof(T) <= 16) {
-            constexpr uint64_t E = 16 / sizeof(T);
-            uint64_t head = ((16 - (ao & 15)) & 15) / sizeof(T);
-            if (head > count)
-                head = count;
-            const uint64_t npk = (count - head) / E;
-            const uint64_t tail_start = head + npk * E;
-            const uint32_t ntail = (uint32_t) (count - tail_start);
-            const unsigned grid = grid_for((uint64_t) cfg.block, npk, cfg.max_grid, cfg.block);
-            set_store_policy(p, cfg, grid);
-            if ((ai & 15) == (ao & 15) && (ar & 15) == (ao & 15))
-                hipLaunchKernelGGL((k_getacc<C, MPIX_REDOP_NT_LOAD, MPIX_REDOP_NT_STORE, true>),
-                                   dim3(grid), dim3(cfg.block), 0, s, tin, tres, tio, head, npk,
-                                   tail_start, ntail, p, grid, (uint32_t) cfg.block);
-            else
-                hipLaunchKernelGGL((k_getacc<C, MPIX_REDOP_NT_LOAD, MPIX_REDOP_NT_STORE, false>),
-                                   dim3(grid), dim3(cfg.block), 0, s, tin, tres, tio, head, npk,
-                                   tail_start, ntail, p, grid, (uint32_t) cfg.block);
-        }
-    } else {
-        const unsigned grid = grid_for((uint64_t) cfg.block * 4, count, cfg.max_grid, cfg.block);
-        hipLaunchKernelGGL((k_getacc_elem<C>), dim3(grid), dim3(cfg.block), 0, s, tin, tres, tio,
-                           count, p, grid, (uint32_t) cfg.block);
+    const LaunchPlan pl = plan_getacc(addr(in), addr(res), addr(io), sizeof(T), count, cfg);
+    const PacketSplit &sp = pl.split;
+    if (pl.form == Form::GetaccElem) {
+        hipLaunchKernelGGL((k_getacc_elem<C>), dim3(pl.grid), dim3(pl.block), 0, s, tin, tres, tio,
+                           count, p, pl.grid, pl.block);
+    } else if constexpr (sizeof(T) <= 16) {
+        set_store_policy(p, cfg, pl.grid);
+        if (pl.form == Form::GetaccAligned)
+            hipLaunchKernelGGL((k_getacc<C, MPIX_REDOP_NT_LOAD, MPIX_REDOP_NT_STORE, true>),
+                               dim3(pl.grid), dim3(pl.block), 0, s, tin, tres, tio, sp.head, sp.npk,
+                               sp.tail_start, sp.ntail, p, pl.grid, pl.block);
+        else
+            hipLaunchKernelGGL((k_getacc<C, MPIX_REDOP_NT_LOAD, MPIX_REDOP_NT_STORE, false>),
+                               dim3(pl.grid), dim3(pl.block), 0, s, tin, tres, tio, sp.head, sp.npk,
+                               sp.tail_start, sp.ntail, p, pl.grid, pl.block);
     }
     return hipGetLastError();
 }

@@ -433,6 +433,101 @@ int MPIX_Get_accumulate_local_plan_async(const void *origin, void *result, void 
 int MPIX_Get_accumulate_local_plan(const void *origin, void *result, void *target,
                                    MPIX_Iov_plan plan, MPIX_Op op);
 
+/* ---- a datatype on every side: typed accumulate and get-accumulate ----
+ * MPI_Accumulate and MPI_Get_accumulate (MPI_Put and MPI_Get are their
+ * MPI_REPLACE / MPI_NO_OP cases) carry a datatype for the origin, the result
+ * and the target.  The reference packs a derived origin into a buffer of its
+ * own before the op (posix_rma.h:39-74: MPL_malloc, MPIR_Typerep_pack,
+ * MPIR_Typerep_op) and serves a derived result with MPIR_Localcopy (:366).
+ * Here each side is a committed plan and the call is one pass: no scratch
+ * buffer, every element read or written once.
+ *
+ * For every packed index p < elements, in each plan's own call order:
+ *   result element p = target element p (its value before the call)
+ *   target element p = target element p OP origin element p
+ * with the target in the inout role and the origin in the in role of the
+ * combiner, exactly as in every other entry.  MPIX_Accumulate_local_typed* has
+ * no result.  The result receives the type map only (padded pairs member by
+ * member); result, target and origin keep their own padding and gap bytes,
+ * which are never loaded or stored.
+ *
+ * A NULL origin_plan or result_plan means that operand is packed; with both
+ * NULL the call leaves exactly the bits of MPIX_Reduce_local_plan* /
+ * MPIX_Get_accumulate_local_plan*.  One plan handle may serve several roles of
+ * one call.  MPI_NO_OP: the accumulate form does nothing; the fetch form is
+ * MPI_Get into a derived result, and neither origin nor origin_plan is looked
+ * at.  MPI_REPLACE: the accumulate form is MPI_Put with derived origin and
+ * target, the fetch form the swap.  MPIX_EQUAL is no accumulate op.
+ *
+ * The packed-order table.  A plan's device table is grouped by residue and
+ * driven from the target side; finding packed element p of the origin or the
+ * result needs one table over all merged runs in call order: the packed
+ * elements before each run, each run's byte offset, and one 32-bit run index
+ * per 256 packed elements.  It is built with the plan (host work only) and is a
+ * per-device allocation of its own, beside the tables MPIX_Iov_plan_info
+ * reports.  A plan of at most one run keeps none.
+ *   MPIX_Iov_plan_locate        the byte offset, relative to the buffer
+ *     pointer, of packed element packed_index, through the lookup function the
+ *     kernels use.  Host only, no HIP call.  A NULL plan or byte_offset is
+ *     MPI_ERR_ARG, an index outside [0, elements) MPI_ERR_COUNT.
+ *   MPIX_Iov_plan_info_packed   the bytes of packed-order table one device
+ *     holds: (2 runs + 1) * 8 + (ceil(elements / 256) + 1) * 4, or 0 for a plan
+ *     of at most one run.
+ *   MPIX_Iov_plan_prepare_packed copies that table to `device` (-1: the current
+ *     one): blocking, idempotent and thread-safe like MPIX_Iov_plan_prepare.  A
+ *     launch that finds the table of an origin or result plan missing uploads it
+ *     itself first.  So ONLY CALLS MADE AFTER prepare_packed FOR THE ORIGIN AND
+ *     RESULT PLANS AND AFTER MPIX_Iov_plan_prepare FOR THE TARGET PLAN are free
+ *     of allocation, copies and waits, and only those may be captured in a
+ *     graph.  MPIX_Iov_plan_free releases it.
+ *
+ * Checks, all before any device work, in this order:
+ *   1. a NULL target_plan (MPI_ERR_ARG);
+ *   2. a non-builtin op, an illegal (op, target plan type) or MPIX_EQUAL
+ *      (MPI_ERR_OP);
+ *   3. every examined non-NULL plan, the origin's and then the result's (the
+ *      origin's is not examined under MPI_NO_OP): an internal type other than
+ *      the target plan's (MPI_ERR_TYPE), then an element count other than its
+ *      (MPI_ERR_COUNT) -- MPI requires matching type signatures;
+ *   4. zero elements then succeeds without looking at a pointer;
+ *   5. NULL or MPI_IN_PLACE operands, the origin exempt under MPI_NO_OP
+ *      (MPI_ERR_BUFFER);
+ *   6. any pairwise overlap among the three BOUNDING byte ranges -- each plan's
+ *      [lo_byte, hi_byte), or the packed range where the plan is NULL
+ *      (MPI_ERR_BUFFER).  O(1); it refuses interleaved layouts whose bytes do not
+ *      actually overlap, which is the rule the target already follows in the
+ *      plan entries.  Runs overlapping one another inside the result or the
+ *      target layout remain the caller's contract;
+ *   7. a legal pair without a kernel (bf16 other than SUM: MPI_ERR_TYPE);
+ *   8. an operand the stream's device cannot dereference (MPI_ERR_BUFFER).
+ *
+ * One launch per residue group of the TARGET plan.  When every side is packed
+ * or one run, the call goes down the contiguous entries' path
+ * (MPIX_Reduce_local_async, MPIX_Get_accumulate_local_async) with each buffer
+ * at its run's offset, and the note above about the split combiners' per-stream
+ * fixup buffer applies to the accumulate form again.
+ *
+ * The async forms take what a kernel on `stream` can dereference.  The sync
+ * forms need a device-memory target, run on the calling thread's library
+ * stream and return when target and result are visible, as
+ * MPIX_Get_accumulate_local_plan. */
+int MPIX_Iov_plan_locate(MPIX_Iov_plan plan, MPIX_Aint packed_index, MPIX_Aint *byte_offset);
+int MPIX_Iov_plan_prepare_packed(MPIX_Iov_plan plan, int device);
+int MPIX_Iov_plan_info_packed(MPIX_Iov_plan plan, MPIX_Aint *table_bytes);
+
+int MPIX_Accumulate_local_typed_async(const void *origin, MPIX_Iov_plan origin_plan,
+                                      void *target, MPIX_Iov_plan target_plan,
+                                      MPIX_Op op, void *stream);
+int MPIX_Accumulate_local_typed(const void *origin, MPIX_Iov_plan origin_plan,
+                                void *target, MPIX_Iov_plan target_plan, MPIX_Op op);
+int MPIX_Get_accumulate_local_typed_async(const void *origin, MPIX_Iov_plan origin_plan,
+                                          void *result, MPIX_Iov_plan result_plan,
+                                          void *target, MPIX_Iov_plan target_plan,
+                                          MPIX_Op op, void *stream);
+int MPIX_Get_accumulate_local_typed(const void *origin, MPIX_Iov_plan origin_plan,
+                                    void *result, MPIX_Iov_plan result_plan,
+                                    void *target, MPIX_Iov_plan target_plan, MPIX_Op op);
+
 /* ---- compare-and-swap ----
  * The local step of MPI_Compare_and_swap on one element (posix_rma.h:605-608,
  * mpidig_rma_callbacks.c:1059-1068):

@@ -17,9 +17,10 @@ def __getattr__(name):
     if name in ('redop', 'coll'):
         import importlib
         return importlib.import_module('.' + name, __name__)
-    # the committed iov plans of mpich_amd.redop, under the package's own name
-    # and the element-atomic entries
+    # the committed iov plans of mpich_amd.redop, under the package's own name,
+    # the typed entries over them and the element-atomic entries
     if name in ('IovPlan', 'reduce_local_plan', 'get_accumulate_local_plan',
+                'accumulate_local_typed', 'get_accumulate_local_typed',
                 'accumulate_local_atomic', 'get_accumulate_local_atomic',
                 'compare_and_swap_local_atomic', 'accumulate_atomic_is_supported'):
         import importlib

@@ -297,6 +297,13 @@ const mpix::PlanEntry *plan_entry(uint32_t opi, uint32_t it)
     return entry_of(mpix::lookup_plan_fp, mpix::lookup_plan_int, mpix::lookup_plan_pair, opi, it);
 }
 
+// ... and of the typed entries (a datatype on every side)
+const mpix::TypedEntry *typed_entry(uint32_t opi, uint32_t it)
+{
+    return entry_of(mpix::lookup_typed_fp, mpix::lookup_typed_int, mpix::lookup_typed_pair, opi,
+                    it);
+}
+
 // ---------------------------------------------------------------- state
 std::atomic<long long> g_ftrue{1}, g_ffalse{0};
 // One-wave (64-thread) blocks of one packet per lane (round 5): kernel-trace
@@ -1757,15 +1764,22 @@ bool missing_operand(const void *origin, const void *result, const void *target,
     return (fetch && no_buffer(result)) || no_buffer(target) || (reads_origin && no_buffer(origin));
 }
 
-// The overlap check: the packed result and origin (`packed` bytes each)
-// against the target's bounding range (`span` bytes from target_lo) and
-// against each other.
+// The overlap check: the byte ranges of result and origin against the target's
+// bounding range (`span` bytes from target_lo) and against each other.
+bool operands_overlap(const void *origin, uint64_t origin_bytes, const void *result,
+                      uint64_t result_bytes, const void *target_lo, uint64_t span, bool fetch,
+                      bool reads_origin)
+{
+    return (fetch && ranges_overlap(result, result_bytes, target_lo, span)) ||
+           (reads_origin && (ranges_overlap(origin, origin_bytes, target_lo, span) ||
+                             (fetch && ranges_overlap(origin, origin_bytes, result, result_bytes))));
+}
+
+// ... with result and origin packed (`packed` bytes each)
 bool operands_overlap(const void *origin, const void *result, const void *target_lo,
                       uint64_t packed, uint64_t span, bool fetch, bool reads_origin)
 {
-    return (fetch && ranges_overlap(result, packed, target_lo, span)) ||
-           (reads_origin && (ranges_overlap(origin, packed, target_lo, span) ||
-                             (fetch && ranges_overlap(origin, packed, result, packed))));
+    return operands_overlap(origin, packed, result, packed, target_lo, span, fetch, reads_origin);
 }
 
 // The operands as a kernel on the stream dereferences them (reachable): filled
@@ -2452,8 +2466,12 @@ struct MPIX_Iov_plan_s {
     std::vector<int32_t> tile;      // every group's tile index, group g from tile_base[g]
     std::vector<size_t> tile_base;
     size_t table_bytes = 0;         // device bytes: rt.tab, then tile (0: nothing to upload)
+    // the packed-order table (redop_packed.h) over all merged runs in call
+    // order, as one device holds it: prefix, off, tile (empty for nrun <= 1)
+    std::vector<char> pk;
     std::mutex mu;
     std::atomic<char *> dev[kMaxDev];
+    std::atomic<char *> pk_dev[kMaxDev];
 };
 
 // Merge, group and index the runs of a table whose type is already resolved.
@@ -2510,6 +2528,8 @@ static int plan_build(std::vector<Run> &runs, uint32_t it, uint64_t ext, MPIX_Io
     MPIX_Iov_plan_s *p = new MPIX_Iov_plan_s;
     for (auto &d : p->dev)
         d.store(nullptr, std::memory_order_relaxed);
+    for (auto &d : p->pk_dev)
+        d.store(nullptr, std::memory_order_relaxed);
     p->it = it;
     p->ext = ext;
     p->total = total;
@@ -2519,6 +2539,27 @@ static int plan_build(std::vector<Run> &runs, uint32_t it, uint64_t ext, MPIX_Io
     if (m == 1)
         p->one_off = runs[0].off;
     if (m > 1) {        // a single run takes the contiguous path: no table
+        // the packed-order table of the merged runs, tile as the groups' below
+        p->pk.resize(mpix::packed_tab_bytes((int64_t) m, total));
+        {
+            int64_t *prefix = (int64_t *) p->pk.data(), *off = prefix + m + 1;
+            int32_t *tl = (int32_t *) (off + m);
+            int64_t pre = 0;
+            for (size_t k = 0; k < m; ++k) {
+                prefix[k] = pre;
+                off[k] = runs[k].off;
+                pre += runs[k].n;
+            }
+            prefix[m] = pre;
+            const uint64_t ntile = (total + 255) / 256;
+            size_t s = 0;
+            for (uint64_t t = 0; t < ntile; ++t) {
+                while (s + 1 < m && (uint64_t) prefix[s + 1] <= t * 256)
+                    ++s;
+                tl[t] = (int32_t) s;
+            }
+            tl[ntile] = (int32_t) (m - 1);
+        }
         group_runs(runs, e, &p->rt);
         const size_t ng = p->rt.resid.size();
         p->tile_base.resize(ng);
@@ -2580,55 +2621,106 @@ int MPIX_Iov_plan_create_iovec(MPIX_Aint nseg, const MPIX_Aint *iov_offsets,
     return set_err(plan_build(runs, it, extent_of(it), plan));
 }
 
-// The plan's tables on `dev`, uploaded if they are not there yet (blocking).
-static int plan_tables(MPIX_Iov_plan_s *p, int dev, char **tab)
+// One of the plan's two table sets on `dev` (`slot`: dev[] or pk_dev[]; `bytes`
+// in all, the first `na` from `a`, the rest from `b`), uploaded if it is not
+// there yet (blocking), published with a release store behind the plan's mutex.
+static int plan_upload(MPIX_Iov_plan_s *p, std::atomic<char *> *slot, int dev, size_t bytes,
+                       const void *a, size_t na, const void *b, char **tab)
 {
     *tab = nullptr;
     if (dev < 0 || dev >= kMaxDev)
         return MPIX_REDOP_ERR_OTHER;
-    if (p->table_bytes == 0)
+    if (bytes == 0)
         return MPIX_REDOP_SUCCESS;
-    if ((*tab = p->dev[dev].load(std::memory_order_acquire)))
+    if ((*tab = slot[dev].load(std::memory_order_acquire)))
         return MPIX_REDOP_SUCCESS;
     std::lock_guard<std::mutex> l(p->mu);
-    if ((*tab = p->dev[dev].load(std::memory_order_acquire)))
+    if ((*tab = slot[dev].load(std::memory_order_acquire)))
         return MPIX_REDOP_SUCCESS;
     DeviceGuard guard(dev);
     char *d = nullptr;
-    int rc = hip_err(hipMalloc((void **) &d, p->table_bytes));
+    int rc = hip_err(hipMalloc((void **) &d, bytes));
     if (rc != MPIX_REDOP_SUCCESS) {
         (void) hipGetLastError();
         return rc;
     }
-    const size_t tb = p->rt.tab.size() * sizeof(int64_t);
-    rc = hip_err(hipMemcpy(d, p->rt.tab.data(), tb, hipMemcpyHostToDevice));
-    if (rc == MPIX_REDOP_SUCCESS)
-        rc = hip_err(hipMemcpy(d + tb, p->tile.data(), p->tile.size() * sizeof(int32_t),
-                               hipMemcpyHostToDevice));
+    rc = hip_err(hipMemcpy(d, a, na, hipMemcpyHostToDevice));
+    if (rc == MPIX_REDOP_SUCCESS && bytes > na)
+        rc = hip_err(hipMemcpy(d + na, b, bytes - na, hipMemcpyHostToDevice));
     if (rc != MPIX_REDOP_SUCCESS) {
         (void) hipFree(d);
         return rc;
     }
-    p->dev[dev].store(d, std::memory_order_release);
+    slot[dev].store(d, std::memory_order_release);
     *tab = d;
     return MPIX_REDOP_SUCCESS;
 }
 
-int MPIX_Iov_plan_prepare(MPIX_Iov_plan plan, int device)
+// The plan's residue-group tables on `dev`: rt.tab, then tile.
+static int plan_tables(MPIX_Iov_plan_s *p, int dev, char **tab)
+{
+    return plan_upload(p, p->dev, dev, p->table_bytes, p->rt.tab.data(),
+                       p->rt.tab.size() * sizeof(int64_t), p->tile.data(), tab);
+}
+
+// ... and its packed-order table.
+static int plan_packed(MPIX_Iov_plan_s *p, int dev, char **tab)
+{
+    return plan_upload(p, p->pk_dev, dev, p->pk.size(), p->pk.data(), p->pk.size(), nullptr, tab);
+}
+
+// MPIX_Iov_plan_prepare[_packed]: the device argument resolved, then `upload`.
+static int plan_prepare(MPIX_Iov_plan plan, int device,
+                        int (*upload)(MPIX_Iov_plan_s *, int, char **))
 {
     if (!plan)
-        return set_err(MPIX_REDOP_ERR_ARG);
+        return MPIX_REDOP_ERR_ARG;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
         (void) hipGetLastError();
-        return set_err(MPIX_REDOP_ERR_OTHER);
+        return MPIX_REDOP_ERR_OTHER;
     }
     if (device == -1 && hipGetDevice(&device) != hipSuccess)
-        return set_err(MPIX_REDOP_ERR_OTHER);
+        return MPIX_REDOP_ERR_OTHER;
     if (device < 0 || device >= ndev)
-        return set_err(MPIX_REDOP_ERR_ARG);
+        return MPIX_REDOP_ERR_ARG;
     char *tab;
-    return set_err(plan_tables(plan, device, &tab));
+    return upload(plan, device, &tab);
+}
+
+int MPIX_Iov_plan_prepare(MPIX_Iov_plan plan, int device)
+{
+    return set_err(plan_prepare(plan, device, plan_tables));
+}
+
+int MPIX_Iov_plan_prepare_packed(MPIX_Iov_plan plan, int device)
+{
+    return set_err(plan_prepare(plan, device, plan_packed));
+}
+
+int MPIX_Iov_plan_info_packed(MPIX_Iov_plan plan, MPIX_Aint *table_bytes)
+{
+    if (!plan)
+        return set_err(MPIX_REDOP_ERR_ARG);
+    if (table_bytes)
+        *table_bytes = (MPIX_Aint) plan->pk.size();
+    return set_err(MPIX_REDOP_SUCCESS);
+}
+
+int MPIX_Iov_plan_locate(MPIX_Iov_plan plan, MPIX_Aint packed_index, MPIX_Aint *byte_offset)
+{
+    if (!plan || !byte_offset)
+        return set_err(MPIX_REDOP_ERR_ARG);
+    if (packed_index < 0 || (uint64_t) packed_index >= plan->total)
+        return set_err(MPIX_REDOP_ERR_COUNT);
+    if (plan->nrun == 1) {
+        *byte_offset = (MPIX_Aint) (plan->one_off + (int64_t) packed_index * (int64_t) plan->ext);
+    } else {
+        const mpix::PackedTab t(plan->pk.data(), plan->nrun);
+        *byte_offset = (MPIX_Aint) mpix::packed_byte(t.prefix, t.off, t.tile,
+                                                     (uint64_t) packed_index, (int64_t) plan->ext);
+    }
+    return set_err(MPIX_REDOP_SUCCESS);
 }
 
 int MPIX_Iov_plan_info(MPIX_Iov_plan plan, MPIX_Aint *elements, MPIX_Aint *runs, MPIX_Aint *groups,
@@ -2661,12 +2753,14 @@ int MPIX_Iov_plan_free(MPIX_Iov_plan *plan)
         return set_err(MPIX_REDOP_SUCCESS);
     int rc = MPIX_REDOP_SUCCESS;
     for (int d = 0; d < kMaxDev; ++d) {
-        char *t = p->dev[d].load(std::memory_order_acquire);
-        if (!t)
-            continue;
-        DeviceGuard guard(d);
-        const int rc2 = hip_err(hipFree(t));
-        rc = rc ? rc : rc2;
+        for (char *t : {p->dev[d].load(std::memory_order_acquire),
+                        p->pk_dev[d].load(std::memory_order_acquire)}) {
+            if (!t)
+                continue;
+            DeviceGuard guard(d);
+            const int rc2 = hip_err(hipFree(t));
+            rc = rc ? rc : rc2;
+        }
     }
     delete p;
     return set_err(rc);
@@ -2785,6 +2879,170 @@ int MPIX_Get_accumulate_local_plan(const void *origin, void *result, void *targe
                                    MPIX_Iov_plan plan, MPIX_Op op)
 {
     return set_err(plan_run(origin, result, target, plan, (uint32_t) op, true, true, nullptr));
+}
+
+// ------------------------------------- a datatype on every side
+// MPIX_[Get_]accumulate_local_typed*: origin and result as plans too (NULL:
+// packed).  One side of such a call: its buffer, its plan and, from them, the
+// bounding byte range the overlap check looks at and the base and table the
+// kernels address it with.
+struct TypedSide {
+    const void *buf;
+    MPIX_Iov_plan_s *plan;
+    // (an operand the op does not read may be NULL: no pointer arithmetic on it)
+    const void *lo() const
+    {
+        return (const void *) ((uintptr_t) buf + (uintptr_t) (plan ? plan->lo : 0));
+    }
+    uint64_t span(uint64_t packed) const
+    {
+        return plan ? (uint64_t) (plan->hi - plan->lo) : packed;
+    }
+    bool table() const { return plan && plan->nrun > 1; }
+    int64_t one_off() const { return plan && plan->nrun == 1 ? plan->one_off : 0; }
+};
+
+// Checks 1-7 of the typed entries (mpix_redop.h), none of which needs a device.
+// *n = 0 when there is nothing to do.
+static int typed_validate(const TypedSide &o, const TypedSide &r, const void *target,
+                          MPIX_Iov_plan_s *tp, uint32_t op, bool fetch, uint64_t *n)
+{
+    *n = 0;
+    if (!tp)
+        return MPIX_REDOP_ERR_ARG;
+    if (!is_builtin_op(op) || (op & 0xf) == kOpEqual || !internal_ok(op, tp->it))
+        return MPIX_REDOP_ERR_OP;
+    const uint32_t opi = op & 0xf;
+    const bool reads_origin = opi != kOpNoOp;
+    for (const MPIX_Iov_plan_s *q : {o.plan, r.plan}) {
+        if (q && q->it != tp->it)
+            return MPIX_REDOP_ERR_TYPE;
+        if (q && q->total != tp->total)
+            return MPIX_REDOP_ERR_COUNT;
+    }
+    if (tp->total == 0)
+        return MPIX_REDOP_SUCCESS;
+    if (missing_operand(o.buf, r.buf, target, fetch, reads_origin))
+        return MPIX_REDOP_ERR_BUFFER;
+    const uint64_t packed = tp->total * tp->ext;
+    if (operands_overlap(o.lo(), o.span(packed), r.lo(), r.span(packed),
+                         (const char *) target + tp->lo, (uint64_t) (tp->hi - tp->lo), fetch,
+                         reads_origin))
+        return MPIX_REDOP_ERR_BUFFER;
+    if (opi < kOpReplace && !typed_entry(opi, tp->it))
+        return MPIX_REDOP_ERR_TYPE;     // a legal pair without a kernel
+    *n = tp->total;
+    return MPIX_REDOP_SUCCESS;
+}
+
+// Validated arguments: operand placement, the device's tables, the launches on
+// `s` -- one per residue group of the target plan; with no table on any side,
+// the contiguous entries' path with each buffer at its run's offset.
+static int typed_enqueue(const TypedSide &o, const TypedSide &r, void *target, MPIX_Iov_plan_s *tp,
+                         uint32_t op, bool fetch, hipStream_t s)
+{
+    const uint32_t opi = op & 0xf;
+    const bool reads_origin = opi != kOpNoOp;
+    Placed q{o.buf, r.buf, target};
+    if (!place_operands(&q, fetch, false, reads_origin, s))
+        return MPIX_REDOP_ERR_BUFFER;
+    if (!fetch && opi == kOpNoOp)
+        return MPIX_REDOP_SUCCESS;
+    const bool otab = reads_origin && o.table(), rtab = fetch && r.table();
+    const char *po = reads_origin ? (const char *) q.origin + o.one_off() : nullptr;
+    char *pr = fetch ? (char *) q.result + r.one_off() : nullptr;
+    if (tp->nrun == 1 && !otab && !rtab) {
+        char *t1 = (char *) q.target + tp->one_off;
+        if (!fetch)
+            return enqueue(Combine{po, t1, tp->total, tp->it, tp->ext, op}, s, q.zc);
+        return getacc_launch(po, pr, t1, tp->total, 1, 1, tp->it, tp->ext, opi, q.zc, s);
+    }
+    const mpix::TypedEntry *en = opi < kOpReplace ? typed_entry(opi, tp->it) : nullptr;
+    if (opi < kOpReplace && !en)
+        return MPIX_REDOP_ERR_TYPE;
+    const int dev = q.launch == -2 ? stream_device(s) : q.launch;
+    char *tab = nullptr, *otb = nullptr, *rtb = nullptr;
+    int rc = plan_tables(tp, dev, &tab);
+    if (rc == MPIX_REDOP_SUCCESS && otab)
+        rc = plan_packed(o.plan, dev, &otb);
+    if (rc == MPIX_REDOP_SUCCESS && rtab)
+        rc = plan_packed(r.plan, dev, &rtb);
+    if (rc != MPIX_REDOP_SUCCESS)
+        return rc;
+    mpix::TypedRuns tr{nullptr, nullptr, 1, tp->total,
+                       otab ? mpix::PackedTab(otb, o.plan->nrun) : mpix::PackedTab(),
+                       rtab ? mpix::PackedTab(rtb, r.plan->nrun) : mpix::PackedTab()};
+    PairMap pm{0, 0};
+    (void) padded_pair(tp->it, &pm);
+    auto launch = [&](void *tg) {
+        if (!en)
+            return hip_err(mpix::launch_typed_copy(copy_mode(opi, fetch), (uint32_t) tp->ext,
+                                                   pm.value_bytes, pm.loc_off, po, pr, tg, tr,
+                                                   launch_cfg(), s));
+        if (fetch)
+            return hip_err(en->getacc(po, pr, tg, tr, params(), launch_cfg(), s));
+        return hip_err(en->acc(po, tg, tr, params(), launch_cfg(), s));
+    };
+    if (tp->nrun == 1)
+        return launch((char *) q.target + tp->one_off);
+    const int32_t *tiles = (const int32_t *) (tab + tp->rt.tab.size() * sizeof(int64_t));
+    for (size_t g = 0; g < tp->rt.resid.size() && rc == MPIX_REDOP_SUCCESS; ++g) {
+        const ResidueGroup gr(tp->rt, g, (const int64_t *) tab);
+        tr.d_tab = gr.seg_off;      // the group's whole table
+        tr.d_tile = tiles + tp->tile_base[g];
+        tr.nseg = gr.n;
+        tr.total = gr.total;
+        rc = launch((char *) q.target + gr.resid);
+    }
+    return rc;
+}
+
+// Either form of the accumulate (fetch = false, no result) and of the fetch entry.
+static int typed_run(const void *origin, MPIX_Iov_plan origin_plan, void *result,
+                     MPIX_Iov_plan result_plan, void *target, MPIX_Iov_plan target_plan, uint32_t op,
+                     bool fetch, bool sync, hipStream_t stream)
+{
+    // under MPI_NO_OP neither origin nor origin_plan is looked at
+    const bool reads_origin = (op & 0xf) != kOpNoOp;
+    const TypedSide o{reads_origin ? origin : nullptr, reads_origin ? origin_plan : nullptr},
+        r{result, result_plan};
+    uint64_t n;
+    int rc = typed_validate(o, r, target, target_plan, op, fetch, &n);
+    if (rc != MPIX_REDOP_SUCCESS || n == 0)
+        return rc;
+    return on_stream(sync, stream, target, [&](hipStream_t s) {
+        return typed_enqueue(o, r, target, target_plan, op, fetch, s);
+    });
+}
+
+int MPIX_Accumulate_local_typed_async(const void *origin, MPIX_Iov_plan origin_plan, void *target,
+                                      MPIX_Iov_plan target_plan, MPIX_Op op, void *stream)
+{
+    return set_err(typed_run(origin, origin_plan, nullptr, nullptr, target, target_plan,
+                             (uint32_t) op, false, false, (hipStream_t) stream));
+}
+
+int MPIX_Accumulate_local_typed(const void *origin, MPIX_Iov_plan origin_plan, void *target,
+                                MPIX_Iov_plan target_plan, MPIX_Op op)
+{
+    return set_err(typed_run(origin, origin_plan, nullptr, nullptr, target, target_plan,
+                             (uint32_t) op, false, true, nullptr));
+}
+
+int MPIX_Get_accumulate_local_typed_async(const void *origin, MPIX_Iov_plan origin_plan,
+                                          void *result, MPIX_Iov_plan result_plan, void *target,
+                                          MPIX_Iov_plan target_plan, MPIX_Op op, void *stream)
+{
+    return set_err(typed_run(origin, origin_plan, result, result_plan, target, target_plan,
+                             (uint32_t) op, true, false, (hipStream_t) stream));
+}
+
+int MPIX_Get_accumulate_local_typed(const void *origin, MPIX_Iov_plan origin_plan, void *result,
+                                    MPIX_Iov_plan result_plan, void *target,
+                                    MPIX_Iov_plan target_plan, MPIX_Op op)
+{
+    return set_err(typed_run(origin, origin_plan, result, result_plan, target, target_plan,
+                             (uint32_t) op, true, true, nullptr));
 }
 
 // ------------------------------------- element-atomic accumulate

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "redop_launch.h"
+#include "redop_packed.h"
 
 namespace mpix {
 
@@ -36,9 +37,9 @@ constexpr int kMaxMultiInputs = 16;
 
 // Each instantiation unit resolves (raw internal type, op index) to an Entry
 // or returns nullptr.  raw = handle & 0xffffff00 for builtins; struct pair
-// handles 0x8c00000k are passed unchanged.  The five kernel families below
-// (Entry, GetaccEntry, GetaccIovEntry, PlanEntry, AtomicEntry) are built from
-// the one (type, op) table of redop_tables.h, each in instantiation units of
+// handles 0x8c00000k are passed unchanged.  The six kernel families below
+// (Entry, GetaccEntry, GetaccIovEntry, PlanEntry, TypedEntry, AtomicEntry) are
+// built from the one (type, op) table of redop_tables.h, each in instantiation units of
 // its own that compile side by side, so a pair has an entry in all of them or
 // in none (AtomicEntry: with null launchers where the unit has no atomic).
 const Entry *lookup_int(int raw, int opi);
@@ -125,6 +126,41 @@ hipError_t launch_plan_copy(CopyMode mode, uint32_t extent, uint32_t value_bytes
                             const void *origin, void *result, void *target, const int64_t *d_tab,
                             const int32_t *d_tile, int64_t nseg, uint64_t total,
                             const LaunchCfg &, hipStream_t);
+
+// Accumulate and get-accumulate with a datatype on every side
+// (MPIX_[Get_]accumulate_local_typed*): one residue group of the TARGET plan
+// drives the launch as in PlanEntry (d_tab == nullptr: a target of one run,
+// target element j = packed element j), and packed element p of the origin and
+// of the result is found through that side's packed-order table (PackedTab,
+// redop_packed.h; a null `prefix`: element p lies at base + p -- a packed
+// operand, or one run whose offset the host has added to the base)
+// (inst_typed_*.hip).
+struct TypedRuns {
+    const int64_t *d_tab;
+    const int32_t *d_tile;
+    int64_t nseg;
+    uint64_t total;
+    PackedTab origin, result;
+};
+
+struct TypedEntry {
+    hipError_t (*acc)(const void *origin, void *target, const TypedRuns &, const Params &,
+                      const LaunchCfg &, hipStream_t);
+    hipError_t (*getacc)(const void *origin, void *result, void *target, const TypedRuns &,
+                         const Params &, const LaunchCfg &, hipStream_t);
+};
+
+const TypedEntry *lookup_typed_int(int raw, int opi);
+const TypedEntry *lookup_typed_fp(int raw, int opi);
+const TypedEntry *lookup_typed_pair(int raw, int opi);
+
+// The type-map copies of the same calls: kCopyFetch gathers the target into the
+// result layout (MPI_Get), kCopySwap also puts the origin's elements in their
+// place, kCopyStore only that (MPI_Put).  Layouts as launch_getacc_iov_copy.
+// inst_typed_copy.hip.
+hipError_t launch_typed_copy(CopyMode mode, uint32_t extent, uint32_t value_bytes, uint32_t loc_off,
+                             const void *origin, void *result, void *target, const TypedRuns &,
+                             const LaunchCfg &, hipStream_t);
 
 // MPI_Compare_and_swap on one integer element of `size` bytes (1, 2, 4, 8,
 // 16): *result = *target; if (*target == *compare) *target = *origin.

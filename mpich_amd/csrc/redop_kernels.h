@@ -1851,6 +1851,179 @@ template <class C> struct MakePlan {
 };
 
 // ---------------------------------------------------------------------------
+// A datatype on every side (MPIX_[Get_]accumulate_local_typed*): k_plan_*'s
+// tile loop over one residue group of the TARGET plan gives the lane its target
+// element and its packed index p; element p of the origin and of the result is
+// then found through that side's packed-order table (packed_run,
+// redop_packed.h: two per-lane loads of its tile index, a search only where a
+// tile spans several runs) at base + off[s] + (p - prefix[s]) elements.  What
+// a side lacks is a null kernel argument, a branch every lane takes alike:
+//   seg_off == nullptr    the target is one run: target element j, p = j
+//   o_prefix / r_prefix   == nullptr: that operand's element p lies at base + p
+//                         (packed, or one run whose offset the host added)
+// -- not template parameters: eight variants per combiner would multiply the
+// build of about a hundred combiners.  Byte offsets keep the alignment plan
+// creation guarantees (4-byte residues, 2 for 2-byte types), which is what the
+// target's own residue already asks of these loads and stores.
+
+// element p of an operand with (prefix != nullptr) or without a table
+template <class T>
+__device__ __forceinline__ T *typed_at(T *base, const int64_t *__restrict__ prefix,
+                                       const int64_t *__restrict__ off,
+                                       const int32_t *__restrict__ tile, uint64_t p)
+{
+    if (!prefix)
+        return base + p;
+    const int64_t s = packed_run(prefix, tile, p);
+    typedef __attribute__((__may_alias__)) char Byte;
+    return reinterpret_cast<T *>((Byte *) base + off[s]) + (p - (uint64_t) prefix[s]);
+}
+
+// target element = target element OP origin element
+template <class C>
+__global__ void __launch_bounds__(256)
+k_typed_acc(const typename C::unit *__restrict__ in, typename C::unit *__restrict__ io,
+            const int64_t *__restrict__ seg_off, const int64_t *__restrict__ prefix,
+            const int64_t *__restrict__ src_off, const int32_t *__restrict__ tile, int64_t nseg,
+            const int64_t *__restrict__ o_prefix, const int64_t *__restrict__ o_off,
+            const int32_t *__restrict__ o_tile, uint64_t total, Params prm, uint32_t nblk)
+{
+    using T = typename C::unit;
+    for (uint64_t t = blockIdx.x; t * 256 < total; t += nblk) {
+        const uint64_t j = t * 256 + threadIdx.x;
+        if (j >= total)
+            break;
+        RunAt r{(int64_t) j, (int64_t) j};
+        if (seg_off)
+            r = run_at(seg_off, prefix, src_off,
+                       plan_run<MPIX_PLAN_LOOKUP>(prefix, tile, nseg, t, j, total), j);
+        const T *pi = typed_at(in, o_prefix, o_off, o_tile, (uint64_t) r.p);
+        io[r.t] = C::apply(io[r.t], *pi, prm);
+    }
+}
+
+// ... and result element = the target element as it was, type map only
+template <class C>
+__global__ void __launch_bounds__(256)
+k_typed_getacc(const typename C::unit *__restrict__ in, typename C::unit *__restrict__ res,
+               typename C::unit *__restrict__ io, const int64_t *__restrict__ seg_off,
+               const int64_t *__restrict__ prefix, const int64_t *__restrict__ src_off,
+               const int32_t *__restrict__ tile, int64_t nseg,
+               const int64_t *__restrict__ o_prefix, const int64_t *__restrict__ o_off,
+               const int32_t *__restrict__ o_tile, const int64_t *__restrict__ r_prefix,
+               const int64_t *__restrict__ r_off, const int32_t *__restrict__ r_tile,
+               uint64_t total, Params prm, uint32_t nblk)
+{
+    using T = typename C::unit;
+    for (uint64_t t = blockIdx.x; t * 256 < total; t += nblk) {
+        const uint64_t j = t * 256 + threadIdx.x;
+        if (j >= total)
+            break;
+        RunAt r{(int64_t) j, (int64_t) j};
+        if (seg_off)
+            r = run_at(seg_off, prefix, src_off,
+                       plan_run<MPIX_PLAN_LOOKUP>(prefix, tile, nseg, t, j, total), j);
+        const T *pi = typed_at(in, o_prefix, o_off, o_tile, (uint64_t) r.p);
+        T *pr = typed_at(res, r_prefix, r_off, r_tile, (uint64_t) r.p);
+        const T a = io[r.t];
+        FetchStore<T>::st(pr, a);
+        io[r.t] = C::apply(a, *pi, prm);
+    }
+}
+
+// MPI_NO_OP / MPI_REPLACE: k_plan_copy's modes and unit bodies (MPI_Get into a
+// derived result, the swap, MPI_Put from a derived origin)
+template <class T, int MODE>
+__global__ void __launch_bounds__(256)
+k_typed_copy(const T *__restrict__ in, T *__restrict__ res, T *__restrict__ io,
+             const int64_t *__restrict__ seg_off, const int64_t *__restrict__ prefix,
+             const int64_t *__restrict__ src_off, const int32_t *__restrict__ tile, int64_t nseg,
+             const int64_t *__restrict__ o_prefix, const int64_t *__restrict__ o_off,
+             const int32_t *__restrict__ o_tile, const int64_t *__restrict__ r_prefix,
+             const int64_t *__restrict__ r_off, const int32_t *__restrict__ r_tile,
+             uint64_t total, uint32_t nblk)
+{
+    for (uint64_t t = blockIdx.x; t * 256 < total; t += nblk) {
+        const uint64_t j = t * 256 + threadIdx.x;
+        if (j >= total)
+            break;
+        RunAt r{(int64_t) j, (int64_t) j};
+        if (seg_off)
+            r = run_at(seg_off, prefix, src_off,
+                       plan_run<MPIX_PLAN_LOOKUP>(prefix, tile, nseg, t, j, total), j);
+        if constexpr (MODE != kPlanScatter) {
+            const T a = io[r.t];
+            FetchStore<T>::st(typed_at(res, r_prefix, r_off, r_tile, (uint64_t) r.p), a);
+        }
+        if constexpr (MODE != kPlanGather) {
+            const T b = *typed_at(in, o_prefix, o_off, o_tile, (uint64_t) r.p);
+            FetchStore<T>::st(io + r.t, b);
+        }
+    }
+}
+
+// The target group's table: RunGroup of d_tab, or all null for a one-run target
+// (nseg = 1 then, so that launch_runs launches).
+struct TypedGroup {
+    const int64_t *seg_off = nullptr, *prefix = nullptr, *src_off = nullptr;
+    int64_t nseg = 1;
+    explicit TypedGroup(const TypedRuns &r)
+    {
+        if (r.d_tab) {
+            const RunGroup g(r.d_tab, r.nseg);
+            seg_off = g.seg_off, prefix = g.prefix, src_off = g.src_off, nseg = r.nseg;
+        }
+    }
+};
+
+template <class C>
+hipError_t launch_typed_acc(const void *in, void *io, const TypedRuns &r, const Params &prm,
+                            const LaunchCfg &cfg, hipStream_t s)
+{
+    using T = typename C::unit;
+    const TypedGroup g(r);
+    return launch_runs(k_typed_acc<C>, g.nseg, r.total, cfg, s, static_cast<const T *>(in),
+                       static_cast<T *>(io), g.seg_off, g.prefix, g.src_off, r.d_tile, g.nseg,
+                       r.origin.prefix, r.origin.off, r.origin.tile, r.total, run_params(prm));
+}
+
+template <class C>
+hipError_t launch_typed_getacc(const void *in, void *res, void *io, const TypedRuns &r,
+                               const Params &prm, const LaunchCfg &cfg, hipStream_t s)
+{
+    using T = typename C::unit;
+    const TypedGroup g(r);
+    return launch_runs(k_typed_getacc<C>, g.nseg, r.total, cfg, s, static_cast<const T *>(in),
+                       static_cast<T *>(res), static_cast<T *>(io), g.seg_off, g.prefix, g.src_off,
+                       r.d_tile, g.nseg, r.origin.prefix, r.origin.off, r.origin.tile,
+                       r.result.prefix, r.result.off, r.result.tile, r.total, run_params(prm));
+}
+
+template <class T>
+hipError_t launch_typed_copy_as(int mode, const void *in, void *res, void *io, const TypedRuns &r,
+                                const LaunchCfg &cfg, hipStream_t s)
+{
+    auto kernel = mode == kPlanGather    ? k_typed_copy<T, kPlanGather>
+                  : mode == kPlanSwap    ? k_typed_copy<T, kPlanSwap>
+                  : mode == kPlanScatter ? k_typed_copy<T, kPlanScatter>
+                                         : nullptr;
+    if (!kernel)
+        return hipErrorInvalidValue;
+    const TypedGroup g(r);
+    return launch_runs(kernel, g.nseg, r.total, cfg, s, static_cast<const T *>(in),
+                       static_cast<T *>(res), static_cast<T *>(io), g.seg_off, g.prefix, g.src_off,
+                       r.d_tile, g.nseg, r.origin.prefix, r.origin.off, r.origin.tile,
+                       r.result.prefix, r.result.off, r.result.tile, r.total);
+}
+
+template <class C> struct MakeTyped {
+    static constexpr TypedEntry get()
+    {
+        return TypedEntry{&launch_typed_acc<C>, &launch_typed_getacc<C>};
+    }
+};
+
+// ---------------------------------------------------------------------------
 // MPI_Compare_and_swap's local step on one element of 1, 2, 4, 8 or 16 bytes
 // (posix_rma.h:605-608): plain loads and stores, stream-ordered like every
 // other entry; the four addresses need no alignment.

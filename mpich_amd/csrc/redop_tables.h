@@ -2,7 +2,8 @@
 //
 // Every kernel family (the reduction's Entry, the fused get-accumulate's
 // GetaccEntry, its iov form's GetaccIovEntry, the committed plans' PlanEntry,
-// the element-atomic accumulate's AtomicEntry of redop_atomic.h)
+// the typed entries' TypedEntry, the element-atomic accumulate's AtomicEntry of
+// redop_atomic.h)
 // builds its three tables from these maps, in its own instantiation units
 // (inst_[<family>_]{int,fp,pair}.hip): E is the family's entry type and
 // Make<C>::get() its entry for combiner C (redop_kernels.h).  So a pair has an

@@ -24,6 +24,7 @@ KOBJS = build/inst_int.o build/inst_fp.o build/inst_pair.o \
         build/inst_getacc_iov_int.o build/inst_getacc_iov_fp.o build/inst_getacc_iov_pair.o \
         build/inst_getacc_copy.o \
         build/inst_plan_int.o build/inst_plan_fp.o build/inst_plan_pair.o build/inst_plan_copy.o \
+        build/inst_typed_int.o build/inst_typed_fp.o build/inst_typed_pair.o build/inst_typed_copy.o \
         build/inst_acc_atomic_int.o build/inst_acc_atomic_fp.o build/inst_acc_atomic_pair.o \
         build/inst_acc_atomic_copy.o
 
@@ -32,7 +33,7 @@ all: $(OUT)/coll_host_sanitize
 $(KOBJS):
 	$(MAKE) -s
 
-$(OUT)/%.o: %.cpp ../../include/mpix_redop.h ../../include/mpix_coll.h redop_dispatch.h redop_launch.h redop_hostpath.h
+$(OUT)/%.o: %.cpp ../../include/mpix_redop.h ../../include/mpix_coll.h redop_dispatch.h redop_launch.h redop_hostpath.h redop_packed.h
 	@mkdir -p $(OUT)
 	$(CXX) $(HOSTFLAGS) $(SANFLAGS) -c $< -o $@
 
@@ -61,6 +62,14 @@ $(OUT)/coll_host_sanitize: ../../tests/c/coll_host_sanitize.c $(OUT)/libmpix_col
 # entries' device-free checks), a goal of its own:
 #   make -f sanitize.mk SAN=asan build/asan/plan_host_check
 $(OUT)/plan_host_check: ../../tests/c/plan_host_check.cpp $(OUT)/libmpix_redop.so
+	$(CXX) -std=c++17 -O1 -g -fno-omit-frame-pointer -Wall $(SANFLAGS) -D__HIP_PLATFORM_AMD__ \
+	    -I../../include -I/opt/rocm/include -o $@ $< -L$(OUT) -lmpix_redop \
+	    -Wl,-rpath,$(abspath $(OUT)) -Wl,-rpath,/opt/rocm/lib
+
+# the typed entries' host side (the packed-order table, MPIX_Iov_plan_locate and
+# the entries' device-free checks):
+#   make -f sanitize.mk SAN=asan build/asan/typed_host_check
+$(OUT)/typed_host_check: ../../tests/c/typed_host_check.cpp $(OUT)/libmpix_redop.so
 	$(CXX) -std=c++17 -O1 -g -fno-omit-frame-pointer -Wall $(SANFLAGS) -D__HIP_PLATFORM_AMD__ \
 	    -I../../include -I/opt/rocm/include -o $@ $< -L$(OUT) -lmpix_redop \
 	    -Wl,-rpath,$(abspath $(OUT)) -Wl,-rpath,/opt/rocm/lib

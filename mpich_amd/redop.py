@@ -76,6 +76,13 @@ def lib():
             'MPIX_Reduce_local_plan': ([vp, vp, vp, i32], i32),
             'MPIX_Get_accumulate_local_plan_async': ([vp, vp, vp, vp, i32, vp], i32),
             'MPIX_Get_accumulate_local_plan': ([vp, vp, vp, vp, i32], i32),
+            'MPIX_Iov_plan_locate': ([vp, aint, ctypes.POINTER(aint)], i32),
+            'MPIX_Iov_plan_prepare_packed': ([vp, i32], i32),
+            'MPIX_Iov_plan_info_packed': ([vp, ctypes.POINTER(aint)], i32),
+            'MPIX_Accumulate_local_typed_async': ([vp, vp, vp, vp, i32, vp], i32),
+            'MPIX_Accumulate_local_typed': ([vp, vp, vp, vp, i32], i32),
+            'MPIX_Get_accumulate_local_typed_async': ([vp, vp, vp, vp, vp, vp, i32, vp], i32),
+            'MPIX_Get_accumulate_local_typed': ([vp, vp, vp, vp, vp, vp, i32], i32),
             'MPIX_Compare_and_swap_local': ([vp, vp, vp, vp, i32], i32),
             'MPIX_Compare_and_swap_local_async': ([vp, vp, vp, vp, i32, vp], i32),
             'MPIX_Accumulate_local_atomic': ([vp, vp, aint, i32, i32], i32),
@@ -430,6 +437,27 @@ class IovPlan:
                                    'table_bytes'), (x.value for x in v)))
         return dict(self._info)
 
+    def locate(self, p):
+        """byte offset, relative to the buffer pointer, of packed element `p`
+        (host only; the lookup the typed kernels use)"""
+        v = ctypes.c_ssize_t()
+        check(lib().MPIX_Iov_plan_locate(self.handle, int(p), ctypes.byref(v)),
+              'MPIX_Iov_plan_locate')
+        return v.value
+
+    def prepare_packed(self, device=-1):
+        """copy the packed-order table (what a typed call needs of its origin
+        and result plans) to `device` (-1: the current one); blocking,
+        idempotent.  Returns an MPI error class."""
+        return lib().MPIX_Iov_plan_prepare_packed(self.handle, int(device))
+
+    def info_packed(self):
+        """bytes of packed-order table one device holds (0: at most one run)"""
+        v = ctypes.c_ssize_t()
+        check(lib().MPIX_Iov_plan_info_packed(self.handle, ctypes.byref(v)),
+              'MPIX_Iov_plan_info_packed')
+        return v.value
+
     def close(self):
         if self._h:
             check(lib().MPIX_Iov_plan_free(ctypes.byref(self._h)), 'MPIX_Iov_plan_free')
@@ -481,6 +509,56 @@ def get_accumulate_local_plan(origin, result, target, plan, op, sync=False, stre
     if sync:
         return lib().MPIX_Get_accumulate_local_plan(*args)
     return lib().MPIX_Get_accumulate_local_plan_async(*args, _stream_ptr(stream))
+
+
+def _typed_range(buf, plan, target_plan, what):
+    """one operand of a typed call against its buffer's bounds: its plan's
+    bounding range, or (plan None) the packed bytes of the target plan"""
+    if buf is None:
+        return
+    if plan is None:
+        if target_plan._ext > 0:
+            _range_check(buf, 0, target_plan.info()['elements'] * target_plan._ext,
+                         'packed ' + what)
+        return
+    i = plan.info() if plan._ext > 0 else None
+    if i and i['elements']:
+        _range_check(buf, i['lo_byte'], i['hi_byte'], 'plan ' + what)
+
+
+def accumulate_local_typed(origin, origin_plan, target, target_plan, op, sync=False, stream=None):
+    """MPI_Accumulate's local step with a datatype on both sides: target element
+    p = target element p OP origin element p in each plan's own order.
+    origin_plan None: a packed origin.  MPI_REPLACE is MPI_Put; MPI_NO_OP does
+    nothing.  sync=True: the blocking form (device-memory target)."""
+    _typed_range(target, target_plan, target_plan, 'target')
+    if (op & 0xf) != 0xe:
+        _typed_range(origin, origin_plan, target_plan, 'origin')
+    args = (_addr(origin), None if origin_plan is None else origin_plan.handle, _addr(target),
+            target_plan.handle, H.as_c_int(op))
+    if sync:
+        return lib().MPIX_Accumulate_local_typed(*args)
+    return lib().MPIX_Accumulate_local_typed_async(*args, _stream_ptr(stream))
+
+
+def get_accumulate_local_typed(origin, origin_plan, result, result_plan, target, target_plan, op,
+                               sync=False, stream=None):
+    """MPI_Get_accumulate's local step with a datatype on all three sides: result
+    element p = target element p as it was, target element p = target element
+    p OP origin element p.  A None plan: that operand is packed.  Under
+    MPI_NO_OP (MPI_Get) origin and origin_plan are not looked at."""
+    _typed_range(target, target_plan, target_plan, 'target')
+    _typed_range(result, result_plan, target_plan, 'result')
+    no_op = (op & 0xf) == 0xe
+    if not no_op:
+        _typed_range(origin, origin_plan, target_plan, 'origin')
+    oh = None if no_op or origin_plan is None else origin_plan.handle
+    args = (None if no_op else _addr(origin), oh, _addr(result),
+            None if result_plan is None else result_plan.handle, _addr(target),
+            target_plan.handle, H.as_c_int(op))
+    if sync:
+        return lib().MPIX_Get_accumulate_local_typed(*args)
+    return lib().MPIX_Get_accumulate_local_typed_async(*args, _stream_ptr(stream))
 
 
 def compare_and_swap_local(origin, compare, result, target, datatype, stream=None, sync=False):

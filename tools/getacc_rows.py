@@ -43,7 +43,22 @@ yardstick on the same table, (iov_fetch) MPIX_Get_accumulate_local_iov[ec]_async
 and (iov_reduce) MPIX_Reduce_local_iov[ec]_async; plus the host's wall time of
 MPIX_Iov_plan_create[_iovec] and of MPIX_Iov_plan_prepare (median of 3), and
 what MPIX_Iov_plan_info reports.  Compare the run lookups by running once per
-build: EXTRA_FLAGS=-DMPIX_PLAN_LOOKUP=n."""
+build: EXTRA_FLAGS=-DMPIX_PLAN_LOOKUP=n.
+
+       getacc_rows.py LIBPATH LABEL typed [ROWS]
+Rows A and B with a derived datatype on all three sides
+(MPIX_[Get_]accumulate_local_typed_async), same method.  The target and the
+result have the row's runs; the origin holds the same element total in runs 3/2
+as long (a shorter last one), so its cuts fall elsewhere.  Per row
+(typed_fetch) and (typed_acc) after MPIX_Iov_plan_prepare[_packed], each
+against the composition of the existing entries on the same buffers:
+(comp_fetch) the MPI_NO_OP gather of the origin through its plan, the
+packed-origin MPIX_Get_accumulate_local_plan_async, the MPI_REPLACE scatter of
+the packed result through MPIX_Reduce_local_plan_async; (comp_acc) the gather,
+then MPIX_Reduce_local_plan_async.  The typed forms are rated on 4 N s / 3 N s
+algorithmic bytes, the compositions move 8 N s / 5 N s.  A form `holds` when it
+is not slower than its composition by more than that composition's own batch
+spread (max - min)."""
 import ctypes
 import json
 import os
@@ -356,6 +371,105 @@ def plan_main():
                           rows=rows)))
 
 
+def typed_main():
+    import numpy as np
+    which = sys.argv[4] if len(sys.argv) > 4 else 'AB'
+    L.MPIX_Iov_plan_create.argtypes = [aint, vp, vp, i32, ctypes.POINTER(vp)]
+    L.MPIX_Iov_plan_prepare.argtypes = [vp, i32]
+    L.MPIX_Iov_plan_prepare_packed.argtypes = [vp, i32]
+    L.MPIX_Iov_plan_info.argtypes = [vp] + [ctypes.POINTER(aint)] * 6
+    L.MPIX_Iov_plan_info_packed.argtypes = [vp, ctypes.POINTER(aint)]
+    L.MPIX_Iov_plan_free.argtypes = [ctypes.POINTER(vp)]
+    L.MPIX_Reduce_local_plan_async.argtypes = [vp, vp, vp, i32, vp]
+    L.MPIX_Get_accumulate_local_plan_async.argtypes = [vp, vp, vp, vp, i32, vp]
+    L.MPIX_Accumulate_local_typed_async.argtypes = [vp, vp, vp, vp, i32, vp]
+    L.MPIX_Get_accumulate_local_typed_async.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp]
+    dev = torch.device('cuda', 0)
+    t8, o8, r8 = (torch.empty(1 << 30, dtype=torch.uint8, device=dev) for _ in range(3))
+    po8, pr8 = (torch.empty(1 << 29, dtype=torch.uint8, device=dev) for _ in range(2))
+    s = torch.cuda.current_stream()
+    sp = s.cuda_stream
+    tp, op_, rp, pop, prp = (x.data_ptr() for x in (t8, o8, r8, po8, pr8))
+    dt = H.as_c_int(H.MPI_DOUBLE)
+    op, no_op, replace = (H.as_c_int(x) for x in (H.MPI_SUM, H.MPI_NO_OP, H.MPI_REPLACE))
+    shapes = dict(A=(1024, 65536), B=(131072, 512))
+    rows = []
+
+    def plan_of(lens):
+        """runs of `lens` elements, each followed by a gap of its own length"""
+        lens = np.asarray(lens, np.int64)
+        offs = np.concatenate([[0], np.cumsum(2 * lens * 8)[:-1]]).astype(np.int64)
+        assert int(offs[-1] + lens[-1] * 8) <= 1 << 30
+        h = vp()
+        ok(L.MPIX_Iov_plan_create(len(lens), offs.ctypes.data, lens.ctypes.data, dt,
+                                  ctypes.byref(h)), 'MPIX_Iov_plan_create')
+        return h
+
+    for name in 'AB':
+        if name not in which:
+            continue
+        nruns, n = shapes[name]
+        total = nruns * n
+        on = n * 3 // 2
+        olens = [on] * (total // on) + ([total % on] if total % on else [])
+        tplan, rplan, oplan = plan_of([n] * nruns), plan_of([n] * nruns), plan_of(olens)
+        ok(L.MPIX_Iov_plan_prepare(tplan, 0), 'MPIX_Iov_plan_prepare')
+        for h in (oplan, rplan):
+            ok(L.MPIX_Iov_plan_prepare(h, 0), 'MPIX_Iov_plan_prepare')     # the composition's
+            ok(L.MPIX_Iov_plan_prepare_packed(h, 0), 'MPIX_Iov_plan_prepare_packed')
+        pk = aint()
+        ok(L.MPIX_Iov_plan_info_packed(oplan, ctypes.byref(pk)), 'MPIX_Iov_plan_info_packed')
+        fill(t8, 'fp64', 0x5EED0B21)
+        fill(o8, 'fp64', 0x5EED0B22)
+        torch.cuda.synchronize()
+
+        def typed_fetch():
+            ok(L.MPIX_Get_accumulate_local_typed_async(op_, oplan, rp, rplan, tp, tplan, op, sp),
+               'MPIX_Get_accumulate_local_typed_async')
+
+        def typed_acc():
+            ok(L.MPIX_Accumulate_local_typed_async(op_, oplan, tp, tplan, op, sp),
+               'MPIX_Accumulate_local_typed_async')
+
+        def gather_origin():
+            ok(L.MPIX_Get_accumulate_local_plan_async(None, pop, op_, oplan, no_op, sp),
+               'the origin gather')
+
+        def comp_fetch():
+            gather_origin()
+            ok(L.MPIX_Get_accumulate_local_plan_async(pop, prp, tp, tplan, op, sp),
+               'MPIX_Get_accumulate_local_plan_async')
+            ok(L.MPIX_Reduce_local_plan_async(prp, rp, rplan, replace, sp), 'the result scatter')
+
+        def comp_acc():
+            gather_origin()
+            ok(L.MPIX_Reduce_local_plan_async(pop, tp, tplan, op, sp),
+               'MPIX_Reduce_local_plan_async')
+        t = timed_forms(dict(typed_fetch=typed_fetch, comp_fetch=comp_fetch, typed_acc=typed_acc,
+                             comp_acc=comp_acc), s)
+        med = {k: v[len(v) // 2] for k, v in t.items()}
+        packed = total * 8
+        r = dict(row=name, type='MPI_DOUBLE', op='MPI_SUM', packed_bytes=packed, target_runs=nruns,
+                 result_runs=nruns, origin_runs=len(olens), origin_packed_table_bytes=pk.value)
+        for k, v in t.items():
+            r[k + '_ms'] = round(med[k], 4)
+            r[k + '_spread_ms'] = [round(v[0], 4), round(v[-1], 4)]
+        for form, nbytes in (('fetch', 4), ('acc', 3)):
+            c = t['comp_' + form]
+            r[form + '_ratio_to_comp'] = round(med['typed_' + form] / med['comp_' + form], 4)
+            r[form + '_holds'] = bool(med['typed_' + form] <= med['comp_' + form] + (c[-1] - c[0]))
+            r['typed_%s_TBs' % form] = round(nbytes * packed / (med['typed_' + form] * 1e-3) / 1e12,
+                                             3)
+        rows.append(r)
+        torch.cuda.synchronize()
+        for h in (tplan, rplan, oplan):
+            ok(L.MPIX_Iov_plan_free(ctypes.byref(h)), 'MPIX_Iov_plan_free')
+    L.MPIX_Redop_build_info.restype = ctypes.c_char_p
+    print(json.dumps(dict(label=sys.argv[2], lib=os.path.basename(sys.argv[1]),
+                          build=L.MPIX_Redop_build_info().decode(), batches=BATCHES, reps=REPS,
+                          rows=rows)))
+
+
 def main():
     nbytes = 1 << 30
     dev = torch.device('cuda', 0)
@@ -414,5 +528,7 @@ if __name__ == '__main__':
         iov_main()
     elif len(sys.argv) > 3 and sys.argv[3] == 'plan':
         plan_main()
+    elif len(sys.argv) > 3 and sys.argv[3] == 'typed':
+        typed_main()
     else:
         main()

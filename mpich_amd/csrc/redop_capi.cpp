@@ -24,12 +24,14 @@
 #include <chrono>
 #include <string>
 #include <mutex>
+#include <utility>
 #include <vector>
 
 #include "mpix_redop.h"
 #include "redop_dispatch.h"
 #include "redop_fixup.h"
 #include "redop_hostpath.h"
+#include "redop_runs.h"
 
 using mpix::Entry;
 using mpix::LaunchCfg;
@@ -1548,95 +1550,11 @@ bool reachable(const void *p, hipStream_t s, int *launch, const void **devptr,
 }
 
 // ------------------------------------------- derived targets as runs
-// One uop call of typerep_op_fallback: `n` elements at extent stride from
-// byte offset `off` of inout (may be negative: lb < 0), combined with the
-// next n elements of the packed source.
-struct Run {
-    int64_t off, n;
-};
-
-// The runs of one call grouped by their offset modulo the extent (zero-length
-// runs dropped).  Group g indexes the target in whole elements from
-// target + resid[g]; its table [seg_off n][prefix n+1][src_off n] (n =
-// nrun[g]) starts at tab[base[g]]: element offset of each run, elements of the
-// group before it (prefix[n] = gtotal[g]), and its first element's index in
-// the packed operands, which follow the call's run order.  Host work only.
-struct RunTable {
-    std::vector<int64_t> resid, gtotal, tab;
-    std::vector<size_t> base, nrun;
-};
-
-// Group g of a run table, its arrays read from `tab`: the host table
-// (rt.tab.data()) or a device copy of it.
-struct ResidueGroup : mpix::RunGroup {
-    int64_t n;          // runs
-    uint64_t total;     // packed elements
-    int64_t resid;
-    ResidueGroup(const RunTable &rt, size_t g, const int64_t *tab)
-        : RunGroup(tab + rt.base[g], (int64_t) rt.nrun[g]), n((int64_t) rt.nrun[g]),
-          total((uint64_t) rt.gtotal[g]), resid(rt.resid[g]) {}
-};
-
-// Residues must keep the 4-byte (for smaller types, the extent's) alignment
-// the element loads need.
-bool residues_aligned(const std::vector<Run> &runs, int64_t e)
-{
-    const int64_t align = e < 4 ? e : 4;
-    for (const Run &r : runs)
-        if ((((r.off % e) + e) % e) % align)
-            return false;
-    return true;
-}
-
-void group_runs(const std::vector<Run> &runs, int64_t e, RunTable *rt)
-{
-    std::vector<std::vector<size_t>> groups;
-    for (size_t k = 0; k < runs.size(); ++k) {
-        if (runs[k].n == 0)
-            continue;
-        int64_t r = ((runs[k].off % e) + e) % e;
-        size_t g = 0;
-        while (g < rt->resid.size() && rt->resid[g] != r)
-            ++g;
-        if (g == rt->resid.size()) {
-            rt->resid.push_back(r);
-            groups.emplace_back();
-        }
-        groups[g].push_back(k);
-    }
-    std::vector<int64_t> src_of(runs.size());
-    {
-        int64_t src = 0;
-        for (size_t k = 0; k < runs.size(); ++k) {
-            src_of[k] = src;
-            src += runs[k].n;
-        }
-    }
-    size_t need = 0;
-    for (const auto &g : groups)
-        need += 3 * g.size() + 1;
-    rt->tab.resize(need);
-    rt->base.resize(groups.size());
-    rt->nrun.resize(groups.size());
-    rt->gtotal.resize(groups.size());
-    size_t at = 0;
-    for (size_t g = 0; g < groups.size(); ++g) {
-        const size_t n = groups[g].size();
-        rt->base[g] = at;
-        rt->nrun[g] = n;
-        int64_t pre = 0;
-        for (size_t q = 0; q < n; ++q) {
-            const Run &r = runs[groups[g][q]];
-            rt->tab[at + q] = (r.off - rt->resid[g]) / e;
-            rt->tab[at + n + q] = pre;
-            rt->tab[at + 2 * n + 1 + q] = src_of[groups[g][q]];
-            pre += r.n;
-        }
-        rt->tab[at + 2 * n] = pre;
-        rt->gtotal[g] = pre;
-        at += 3 * n + 1;
-    }
-}
+// The runs, their scan, residue groups and tables and the committed plans'
+// layout: redop_runs.h.  What follows uploads and launches.
+using mpix::ResidueGroup;
+using mpix::Run;
+using mpix::RunTable;
 
 // Upload a run table on `s` through the next of the current device's two
 // slots, shared by the reduce and the fetch forms.  On success *slot holds the
@@ -1688,7 +1606,7 @@ template <class F>
 int launch_groups(const std::vector<Run> &runs, int64_t e, hipStream_t s, F launch)
 {
     RunTable rt;
-    group_runs(runs, e, &rt);
+    mpix::group_runs(runs, e, &rt);
     DevState::IovSlot *sl = nullptr;
     int rc = upload_runs(rt, s, &sl);
     for (size_t g = 0; g < rt.resid.size() && rc == MPIX_REDOP_SUCCESS; ++g)
@@ -1727,7 +1645,7 @@ int enqueue_runs(const void *inbuf, void *inoutbuf, const std::vector<Run> &runs
         inoutbuf = (void *) pio;
     }
     const int64_t e = (int64_t) ext;
-    if (!residues_aligned(runs, e))
+    if (!mpix::residues_aligned(runs, e))
         return MPIX_REDOP_ERR_ARG;
     uint32_t opi = op & 0xf;
     if (opi == kOpNoOp)
@@ -2265,67 +2183,16 @@ int MPIX_Get_accumulate_local_vector(const void *origin, void *result, void *tar
                           (uint32_t) op, true, nullptr));
 }
 
-// The element runs of the flattened-iov forms (seg_counts in elements).
-static int runs_from_iov(MPIX_Aint nseg, const MPIX_Aint *seg_offsets, const MPIX_Aint *seg_counts,
-                         std::vector<Run> *runs)
-{
-    if (nseg < 0)
-        return MPIX_REDOP_ERR_COUNT;
-    if (nseg > 0 && (!seg_offsets || !seg_counts))
-        return MPIX_REDOP_ERR_BUFFER;
-    runs->reserve((size_t) nseg);
-    for (MPIX_Aint s = 0; s < nseg; ++s) {
-        if (seg_counts[s] < 0)
-            return MPIX_REDOP_ERR_COUNT;
-        runs->push_back(Run{seg_offsets[s], seg_counts[s]});
-    }
-    return MPIX_REDOP_SUCCESS;
-}
+// The element runs of a caller's table (redop_runs.h); the iovec form's handle
+// is resolved here, an unknown type going in as extent 0.
+using mpix::runs_from_iov;
 
-// The element runs of the raw-iovec forms (iov_lens in bytes).
 static int runs_from_iovec(MPIX_Aint nseg, const MPIX_Aint *iov_offsets, const MPIX_Aint *iov_lens,
                            uint32_t basic_type, std::vector<Run> *runs)
 {
-    if (nseg < 0)
-        return MPIX_REDOP_ERR_COUNT;
-    if (nseg > 0 && (!iov_offsets || !iov_lens))
-        return MPIX_REDOP_ERR_BUFFER;
-    uint32_t it = to_internal(basic_type);
-    uint64_t ext = extent_of(it), size = size_of(it);
-    if (it == kNull || ext == 0)
-        return MPIX_REDOP_ERR_TYPE;
-    // typerep_op.c:115-149: segments are gathered until they hold one
-    // element's data (pairtypes split by their padding); each call covers
-    // curr_len / size elements laid out at extent stride from target_ptr,
-    // and a partial element left at the end of a segment starts the next one
-    const bool pairtype = size < ext;
-    runs->reserve((size_t) nseg);
-    MPIX_Aint curr = 0, target = 0;
-    for (MPIX_Aint i = 0; i < nseg; ++i) {
-        if (iov_lens[i] < 0)
-            return MPIX_REDOP_ERR_COUNT;
-        if (pairtype) {
-            if (curr == 0)
-                target = iov_offsets[i];
-            curr += iov_lens[i];
-            if (curr < (MPIX_Aint) size)
-                continue;
-        } else {
-            target = iov_offsets[i];
-            curr = iov_lens[i];
-        }
-        MPIX_Aint n = curr / (MPIX_Aint) size;
-        MPIX_Aint data = n * (MPIX_Aint) size;
-        runs->push_back(Run{target, n});
-        if (pairtype) {
-            curr -= data;
-            if (curr > 0)
-                target = iov_offsets[i] + (iov_lens[i] - curr);
-        } else if (curr != data) {
-            return MPIX_REDOP_ERR_ARG;            // the reference's MPIR_Assert (:147)
-        }
-    }
-    return MPIX_REDOP_SUCCESS;
+    const uint32_t it = to_internal(basic_type);
+    return mpix::runs_from_iovec(nseg, iov_offsets, iov_lens, it == kNull ? 0 : size_of(it),
+                                 it == kNull ? 0 : extent_of(it), runs);
 }
 
 int MPIX_Reduce_local_iov_async(const void *inbuf, void *inoutbuf, MPIX_Aint nseg,
@@ -2367,41 +2234,19 @@ static int getacc_runs(const void *origin, void *result, void *target,
     const uint32_t opi = op & 0xf;
     if (opi == kOpEqual)
         return MPIX_REDOP_ERR_OP;       // MPIX_EQUAL is no accumulate op
-    // total elements and the target's bounding byte range [lo, hi): lowest run
-    // start to highest run end, zero-length runs aside; `over` once a packed
-    // operand or that range would reach 2^56 bytes
-    const uint64_t cap = ((uint64_t) 1 << 56) / ext;
-    const __int128 span_cap = (__int128) 1 << 56;
-    uint64_t total = 0;
-    __int128 lo = 0, hi = 0;
-    bool over = false, any = false;
-    for (const Run &r : runs) {
-        if (r.n == 0)
-            continue;
-        if ((uint64_t) r.n > cap || total + (uint64_t) r.n > cap) {
-            over = true;
-            break;
-        }
-        total += (uint64_t) r.n;
-        const __int128 a = r.off, b = a + (__int128) ((uint64_t) r.n * ext);
-        if (!any || a < lo)
-            lo = a;
-        if (!any || b > hi)
-            hi = b;
-        any = true;
-    }
-    if (!over && total == 0)
+    const mpix::RunScan sc = mpix::scan_runs(runs, ext);
+    if (!sc.over && sc.total == 0)
         return MPIX_REDOP_SUCCESS;
     const bool reads_origin = opi != kOpNoOp;
     if (missing_operand(origin, result, target, true, reads_origin))
         return MPIX_REDOP_ERR_BUFFER;
     const int64_t e = (int64_t) ext;
-    if (!residues_aligned(runs, e))
+    if (!mpix::residues_aligned(runs, e))
         return MPIX_REDOP_ERR_ARG;
-    if (over || hi - lo >= span_cap || total * ext >= (uint64_t) span_cap)
+    if (sc.too_long(ext))
         return MPIX_REDOP_ERR_COUNT;
-    if (operands_overlap(origin, result, (const char *) target + (int64_t) lo, total * ext,
-                         (uint64_t) (hi - lo), true, reads_origin))
+    if (operands_overlap(origin, result, (const char *) target + (int64_t) sc.lo, sc.total * ext,
+                         (uint64_t) (sc.hi - sc.lo), true, reads_origin))
         return MPIX_REDOP_ERR_BUFFER;
     const mpix::GetaccIovEntry *en = nullptr;
     if (opi < kOpReplace && !(en = getacc_iov_entry(opi, it)))
@@ -2449,176 +2294,58 @@ int MPIX_Get_accumulate_local_iovec_async(const void *origin, void *result, void
 }
 
 // ------------------------------------------------ committed iov plans
-// What MPI_Type_commit is to a datatype: the runs of one (table, basic type),
-// merged, grouped by residue and indexed per tile once, kept on the host and,
-// after MPIX_Iov_plan_prepare, resident on each device that uses them.  The
+// What MPI_Type_commit is to a datatype: the layout of one (table, basic type)
+// (mpix::PlanLayout, redop_runs.h), kept on the host and, after
+// MPIX_Iov_plan_prepare, resident on each device that uses it.  The
 // plan-taking entries then do no table work, no upload and no event call.
 // Immutable after create apart from `dev` (behind `mu`; a launch reads its
 // device's pointer with one acquire load).
-struct MPIX_Iov_plan_s {
-    uint32_t it = 0;
-    uint64_t ext = 0;
-    uint64_t total = 0;             // packed elements
-    int64_t nrun = 0;               // runs after the merge
-    int64_t lo = 0, hi = 0;         // the target's bounding byte range [lo, hi)
-    int64_t one_off = 0;            // nrun == 1: the run's byte offset
-    RunTable rt;                    // group_runs of the merged runs
-    std::vector<int32_t> tile;      // every group's tile index, group g from tile_base[g]
-    std::vector<size_t> tile_base;
-    size_t table_bytes = 0;         // device bytes: rt.tab, then tile (0: nothing to upload)
-    // the packed-order table (redop_packed.h) over all merged runs in call
-    // order, as one device holds it: prefix, off, tile (empty for nrun <= 1)
-    std::vector<char> pk;
+struct MPIX_Iov_plan_s : mpix::PlanLayout {
     std::mutex mu;
-    std::atomic<char *> dev[kMaxDev];
-    std::atomic<char *> pk_dev[kMaxDev];
+    std::atomic<char *> dev[kMaxDev] = {};
+    std::atomic<char *> pk_dev[kMaxDev] = {};
+    explicit MPIX_Iov_plan_s(mpix::PlanLayout &&lay) : mpix::PlanLayout(std::move(lay)) {}
 };
 
-// Merge, group and index the runs of a table whose type is already resolved.
-static int plan_build(std::vector<Run> &runs, uint32_t it, uint64_t ext, MPIX_Iov_plan *out)
+// Either table form.  *plan = NULL before anything else, nseg > INT_MAX before
+// the table is read (typerep_op.c:111 asserts the same), and the plan pointer
+// is looked at only after the table's own checks.
+static int plan_create(MPIX_Aint nseg, const MPIX_Aint *offsets, const MPIX_Aint *second,
+                       uint32_t basic_type, bool iovec, MPIX_Iov_plan *plan)
 {
-    // total elements and the bounding byte range as the iov entries find them
-    // (getacc_runs): zero-length runs aside; sums through 128 bits, since
-    // n * ext may not fit 64 for a table about to be refused
-    const int64_t e = (int64_t) ext;
-    const uint64_t cap = ((uint64_t) 1 << 56) / ext;
-    const __int128 span_cap = (__int128) 1 << 56;
-    uint64_t total = 0;
-    __int128 lo = 0, hi = 0;
-    bool over = false, any = false;
-    for (const Run &r : runs) {
-        if (r.n == 0)
-            continue;
-        if ((uint64_t) r.n > cap || total + (uint64_t) r.n > cap) {
-            over = true;
-            break;
-        }
-        total += (uint64_t) r.n;
-        const __int128 a = r.off, b = a + (__int128) r.n * e;
-        if (!any || a < lo)
-            lo = a;
-        if (!any || b > hi)
-            hi = b;
-        any = true;
-    }
-    // a table of zero elements is a valid plan whatever its offsets are, as
-    // the entries succeed on it; otherwise every run's residue counts
-    if (over || total != 0) {
-        if (!residues_aligned(runs, e))
-            return MPIX_REDOP_ERR_ARG;
-        if (over || hi - lo >= span_cap || (__int128) total * e >= span_cap)
-            return MPIX_REDOP_ERR_COUNT;
-    }
-    // merge in call order: run k+1 starting where run k ends continues it (its
-    // packed elements follow run k's by construction); zero-length runs drop
-    // out, so one between two such runs does not keep them apart
-    size_t m = 0;
-    for (size_t k = 0; k < runs.size(); ++k) {
-        const Run r = runs[k];
-        if (r.n == 0)
-            continue;
-        if (m > 0 && (__int128) runs[m - 1].off + (__int128) runs[m - 1].n * e == (__int128) r.off)
-            runs[m - 1].n += r.n;
-        else
-            runs[m++] = r;
-    }
-    runs.resize(m);
-    if (!out)
-        return MPIX_REDOP_ERR_ARG;
-    MPIX_Iov_plan_s *p = new MPIX_Iov_plan_s;
-    for (auto &d : p->dev)
-        d.store(nullptr, std::memory_order_relaxed);
-    for (auto &d : p->pk_dev)
-        d.store(nullptr, std::memory_order_relaxed);
-    p->it = it;
-    p->ext = ext;
-    p->total = total;
-    p->nrun = (int64_t) m;
-    p->lo = (int64_t) lo;
-    p->hi = (int64_t) hi;
-    if (m == 1)
-        p->one_off = runs[0].off;
-    if (m > 1) {        // a single run takes the contiguous path: no table
-        // the packed-order table of the merged runs, tile as the groups' below
-        p->pk.resize(mpix::packed_tab_bytes((int64_t) m, total));
-        {
-            int64_t *prefix = (int64_t *) p->pk.data(), *off = prefix + m + 1;
-            int32_t *tl = (int32_t *) (off + m);
-            int64_t pre = 0;
-            for (size_t k = 0; k < m; ++k) {
-                prefix[k] = pre;
-                off[k] = runs[k].off;
-                pre += runs[k].n;
-            }
-            prefix[m] = pre;
-            const uint64_t ntile = (total + 255) / 256;
-            size_t s = 0;
-            for (uint64_t t = 0; t < ntile; ++t) {
-                while (s + 1 < m && (uint64_t) prefix[s + 1] <= t * 256)
-                    ++s;
-                tl[t] = (int32_t) s;
-            }
-            tl[ntile] = (int32_t) (m - 1);
-        }
-        group_runs(runs, e, &p->rt);
-        const size_t ng = p->rt.resid.size();
-        p->tile_base.resize(ng);
-        size_t need = 0;
-        for (size_t g = 0; g < ng; ++g) {
-            p->tile_base[g] = need;
-            need += (size_t) (((uint64_t) p->rt.gtotal[g] + 255) / 256) + 1;
-        }
-        p->tile.resize(need);
-        for (size_t g = 0; g < ng; ++g) {
-            const ResidueGroup gr(p->rt, g, p->rt.tab.data());
-            int32_t *tl = p->tile.data() + p->tile_base[g];
-            const uint64_t ntile = (gr.total + 255) / 256;
-            int64_t s = 0;
-            for (uint64_t t = 0; t < ntile; ++t) {
-                while (s + 1 < gr.n && (uint64_t) gr.prefix[s + 1] <= t * 256)
-                    ++s;
-                tl[t] = (int32_t) s;
-            }
-            tl[ntile] = (int32_t) (gr.n - 1);
-        }
-        p->table_bytes = p->rt.tab.size() * sizeof(int64_t) + p->tile.size() * sizeof(int32_t);
-    }
-    *out = p;
-    return MPIX_REDOP_SUCCESS;
+    if (plan)
+        *plan = nullptr;
+    if (nseg > (MPIX_Aint) INT_MAX)
+        return MPIX_REDOP_ERR_COUNT;
+    std::vector<Run> runs;
+    int rc = iovec ? runs_from_iovec(nseg, offsets, second, basic_type, &runs)
+                   : runs_from_iov(nseg, offsets, second, &runs);
+    if (rc != MPIX_REDOP_SUCCESS)
+        return rc;
+    const uint32_t it = to_internal(basic_type);
+    const uint64_t ext = it == kNull ? 0 : extent_of(it);
+    if (ext == 0)
+        return MPIX_REDOP_ERR_TYPE;
+    mpix::PlanLayout lay;
+    rc = lay.build(runs, it, ext);
+    if (rc == MPIX_REDOP_SUCCESS && !plan)
+        rc = MPIX_REDOP_ERR_ARG;
+    if (rc == MPIX_REDOP_SUCCESS)
+        *plan = new MPIX_Iov_plan_s(std::move(lay));
+    return rc;
 }
 
 int MPIX_Iov_plan_create(MPIX_Aint nseg, const MPIX_Aint *seg_offsets, const MPIX_Aint *seg_counts,
                          MPIX_Datatype basic_type, MPIX_Iov_plan *plan)
 {
-    if (plan)
-        *plan = nullptr;
-    if (nseg > (MPIX_Aint) INT_MAX)
-        return set_err(MPIX_REDOP_ERR_COUNT);       // typerep_op.c:111 asserts the same
-    std::vector<Run> runs;
-    int rc = runs_from_iov(nseg, seg_offsets, seg_counts, &runs);
-    if (rc != MPIX_REDOP_SUCCESS)
-        return set_err(rc);
-    const uint32_t it = to_internal((uint32_t) basic_type);
-    const uint64_t ext = it == kNull ? 0 : extent_of(it);
-    if (ext == 0)
-        return set_err(MPIX_REDOP_ERR_TYPE);
-    return set_err(plan_build(runs, it, ext, plan));
+    return set_err(plan_create(nseg, seg_offsets, seg_counts, (uint32_t) basic_type, false, plan));
 }
 
 int MPIX_Iov_plan_create_iovec(MPIX_Aint nseg, const MPIX_Aint *iov_offsets,
                                const MPIX_Aint *iov_lens, MPIX_Datatype basic_type,
                                MPIX_Iov_plan *plan)
 {
-    if (plan)
-        *plan = nullptr;
-    if (nseg > (MPIX_Aint) INT_MAX)
-        return set_err(MPIX_REDOP_ERR_COUNT);
-    std::vector<Run> runs;
-    int rc = runs_from_iovec(nseg, iov_offsets, iov_lens, (uint32_t) basic_type, &runs);
-    if (rc != MPIX_REDOP_SUCCESS)
-        return set_err(rc);
-    const uint32_t it = to_internal((uint32_t) basic_type);
-    return set_err(plan_build(runs, it, extent_of(it), plan));
+    return set_err(plan_create(nseg, iov_offsets, iov_lens, (uint32_t) basic_type, true, plan));
 }
 
 // One of the plan's two table sets on `dev` (`slot`: dev[] or pk_dev[]; `bytes`
@@ -2659,8 +2386,8 @@ static int plan_upload(MPIX_Iov_plan_s *p, std::atomic<char *> *slot, int dev, s
 // The plan's residue-group tables on `dev`: rt.tab, then tile.
 static int plan_tables(MPIX_Iov_plan_s *p, int dev, char **tab)
 {
-    return plan_upload(p, p->dev, dev, p->table_bytes, p->rt.tab.data(),
-                       p->rt.tab.size() * sizeof(int64_t), p->tile.data(), tab);
+    return plan_upload(p, p->dev, dev, p->table_bytes, p->rt.tab.data(), p->tile_pos(),
+                       p->tile.data(), tab);
 }
 
 // ... and its packed-order table.
@@ -2713,13 +2440,7 @@ int MPIX_Iov_plan_locate(MPIX_Iov_plan plan, MPIX_Aint packed_index, MPIX_Aint *
         return set_err(MPIX_REDOP_ERR_ARG);
     if (packed_index < 0 || (uint64_t) packed_index >= plan->total)
         return set_err(MPIX_REDOP_ERR_COUNT);
-    if (plan->nrun == 1) {
-        *byte_offset = (MPIX_Aint) (plan->one_off + (int64_t) packed_index * (int64_t) plan->ext);
-    } else {
-        const mpix::PackedTab t(plan->pk.data(), plan->nrun);
-        *byte_offset = (MPIX_Aint) mpix::packed_byte(t.prefix, t.off, t.tile,
-                                                     (uint64_t) packed_index, (int64_t) plan->ext);
-    }
+    *byte_offset = (MPIX_Aint) plan->locate((uint64_t) packed_index);
     return set_err(MPIX_REDOP_SUCCESS);
 }
 
@@ -2733,7 +2454,7 @@ int MPIX_Iov_plan_info(MPIX_Iov_plan plan, MPIX_Aint *elements, MPIX_Aint *runs,
     if (runs)
         *runs = (MPIX_Aint) plan->nrun;
     if (groups)     // a single run is one group, though it has no table
-        *groups = plan->nrun == 1 ? 1 : (MPIX_Aint) plan->rt.resid.size();
+        *groups = plan->nrun == 1 ? 1 : (MPIX_Aint) plan->groups();
     if (lo_byte)
         *lo_byte = (MPIX_Aint) plan->lo;
     if (hi_byte)
@@ -2766,126 +2487,9 @@ int MPIX_Iov_plan_free(MPIX_Iov_plan *plan)
     return set_err(rc);
 }
 
-// Checks 1-6 of the plan-taking entries (mpix_redop.h), none of which needs a
-// device.  origin NULL-able: the fetch form under MPI_NO_OP.  *n = 0 when there
-// is nothing to do.
-static int plan_validate(const void *origin, const void *result, const void *target,
-                         MPIX_Iov_plan_s *p, uint32_t op, bool fetch, uint64_t *n)
-{
-    *n = 0;
-    if (!p)
-        return MPIX_REDOP_ERR_ARG;
-    if (!is_builtin_op(op) || (op & 0xf) == kOpEqual || !internal_ok(op, p->it))
-        return MPIX_REDOP_ERR_OP;
-    if (p->total == 0)
-        return MPIX_REDOP_SUCCESS;
-    const uint32_t opi = op & 0xf;
-    const bool reads_origin = !(fetch && opi == kOpNoOp);
-    if (missing_operand(origin, result, target, fetch, reads_origin))
-        return MPIX_REDOP_ERR_BUFFER;
-    if (operands_overlap(origin, result, (const char *) target + p->lo, p->total * p->ext,
-                         (uint64_t) (p->hi - p->lo), fetch, reads_origin))
-        return MPIX_REDOP_ERR_BUFFER;
-    // a plan of one run launches through gpu_entry / getacc_entry instead: every
-    // family is built from the one (type, op) table (redop_tables.h), so one
-    // lookup answers for all
-    if (opi < kOpReplace && !plan_entry(opi, p->it))
-        return MPIX_REDOP_ERR_TYPE;     // a legal pair without a kernel
-    *n = p->total;
-    return MPIX_REDOP_SUCCESS;
-}
-
-// Validated arguments: operand placement, the device's tables, the launches
-// on `s` -- one per residue group; a plan of one run goes down the contiguous
-// entries' path with the target at the run's offset.  result == NULL: the
-// reduce form.
-static int plan_enqueue(const void *origin, void *result, void *target, MPIX_Iov_plan_s *p,
-                        uint32_t op, bool fetch, hipStream_t s)
-{
-    const uint32_t opi = op & 0xf;
-    Placed q{origin, result, target};
-    if (!place_operands(&q, fetch, false, !(fetch && opi == kOpNoOp), s))
-        return MPIX_REDOP_ERR_BUFFER;
-    const void *po = q.origin;
-    void *pr = (void *) q.result;
-    if (!fetch && opi == kOpNoOp)
-        return MPIX_REDOP_SUCCESS;
-    if (p->nrun == 1) {
-        char *t1 = (char *) q.target + p->one_off;
-        if (!fetch)
-            return enqueue(Combine{po, t1, p->total, p->it, p->ext, op}, s, q.zc);
-        return getacc_launch(po, pr, t1, p->total, 1, 1, p->it, p->ext, opi, q.zc, s);
-    }
-    const mpix::PlanEntry *en = opi < kOpReplace ? plan_entry(opi, p->it) : nullptr;
-    if (opi < kOpReplace && !en)
-        return MPIX_REDOP_ERR_TYPE;
-    char *tab;
-    int rc = plan_tables(p, q.launch == -2 ? stream_device(s) : q.launch, &tab);
-    if (rc != MPIX_REDOP_SUCCESS)
-        return rc;
-    PairMap pm{0, 0};
-    (void) padded_pair(p->it, &pm);
-    const int32_t *tiles = (const int32_t *) (tab + p->rt.tab.size() * sizeof(int64_t));
-    for (size_t g = 0; g < p->rt.resid.size() && rc == MPIX_REDOP_SUCCESS; ++g) {
-        const ResidueGroup gr(p->rt, g, (const int64_t *) tab);
-        const int64_t *t = gr.seg_off;      // the group's whole table
-        const int32_t *tl = tiles + p->tile_base[g];
-        void *tg = (char *) q.target + gr.resid;
-        if (!en)
-            rc = hip_err(mpix::launch_plan_copy(copy_mode(opi, fetch), (uint32_t) p->ext,
-                                                pm.value_bytes, pm.loc_off, po, pr, tg, t, tl, gr.n,
-                                                gr.total, launch_cfg(), s));
-        else if (fetch)
-            rc = hip_err(en->getacc(po, pr, tg, t, tl, gr.n, gr.total, params(), launch_cfg(), s));
-        else
-            rc = hip_err(en->reduce(po, tg, t, tl, gr.n, gr.total, params(), launch_cfg(), s));
-    }
-    return rc;
-}
-
-// Either form of the reduce (fetch = false, no result) and the fetch entry.
-static int plan_run(const void *origin, void *result, void *target, MPIX_Iov_plan plan,
-                    uint32_t op, bool fetch, bool sync, hipStream_t stream)
-{
-    uint64_t n;
-    int rc = plan_validate(origin, result, target, plan, op, fetch, &n);
-    if (rc != MPIX_REDOP_SUCCESS || n == 0)
-        return rc;
-    return on_stream(sync, stream, target, [&](hipStream_t s) {
-        return plan_enqueue(origin, result, target, plan, op, fetch, s);
-    });
-}
-
-int MPIX_Reduce_local_plan_async(const void *inbuf, void *inoutbuf, MPIX_Iov_plan plan, MPIX_Op op,
-                                 void *stream)
-{
-    return set_err(plan_run(inbuf, nullptr, inoutbuf, plan, (uint32_t) op, false, false,
-                            (hipStream_t) stream));
-}
-
-int MPIX_Reduce_local_plan(const void *inbuf, void *inoutbuf, MPIX_Iov_plan plan, MPIX_Op op)
-{
-    return set_err(plan_run(inbuf, nullptr, inoutbuf, plan, (uint32_t) op, false, true, nullptr));
-}
-
-int MPIX_Get_accumulate_local_plan_async(const void *origin, void *result, void *target,
-                                         MPIX_Iov_plan plan, MPIX_Op op, void *stream)
-{
-    return set_err(plan_run(origin, result, target, plan, (uint32_t) op, true, false,
-                            (hipStream_t) stream));
-}
-
-int MPIX_Get_accumulate_local_plan(const void *origin, void *result, void *target,
-                                   MPIX_Iov_plan plan, MPIX_Op op)
-{
-    return set_err(plan_run(origin, result, target, plan, (uint32_t) op, true, true, nullptr));
-}
-
-// ------------------------------------- a datatype on every side
-// MPIX_[Get_]accumulate_local_typed*: origin and result as plans too (NULL:
-// packed).  One side of such a call: its buffer, its plan and, from them, the
-// bounding byte range the overlap check looks at and the base and table the
-// kernels address it with.
+// One side of a plan-taking call: its buffer, its plan (NULL: packed) and, from
+// them, the bounding byte range the overlap check looks at and the base and
+// table the kernels address it with.
 struct TypedSide {
     const void *buf;
     MPIX_Iov_plan_s *plan;
@@ -2902,10 +2506,13 @@ struct TypedSide {
     int64_t one_off() const { return plan && plan->nrun == 1 ? plan->one_off : 0; }
 };
 
-// Checks 1-7 of the typed entries (mpix_redop.h), none of which needs a device.
-// *n = 0 when there is nothing to do.
-static int typed_validate(const TypedSide &o, const TypedSide &r, const void *target,
-                          MPIX_Iov_plan_s *tp, uint32_t op, bool fetch, uint64_t *n)
+// The device-free checks of the plan entries (1-6) and of the typed entries
+// (1-7, mpix_redop.h): one list, the plan entries' sides being packed (no side
+// plan).  reads_origin is the caller's rule (plan_run).  *n = 0 when there is
+// nothing to do.
+static int plan_validate(const TypedSide &o, const TypedSide &r, const void *target,
+                         MPIX_Iov_plan_s *tp, uint32_t op, bool fetch, bool reads_origin,
+                         uint64_t *n)
 {
     *n = 0;
     if (!tp)
@@ -2913,7 +2520,6 @@ static int typed_validate(const TypedSide &o, const TypedSide &r, const void *ta
     if (!is_builtin_op(op) || (op & 0xf) == kOpEqual || !internal_ok(op, tp->it))
         return MPIX_REDOP_ERR_OP;
     const uint32_t opi = op & 0xf;
-    const bool reads_origin = opi != kOpNoOp;
     for (const MPIX_Iov_plan_s *q : {o.plan, r.plan}) {
         if (q && q->it != tp->it)
             return MPIX_REDOP_ERR_TYPE;
@@ -2929,7 +2535,10 @@ static int typed_validate(const TypedSide &o, const TypedSide &r, const void *ta
                          (const char *) target + tp->lo, (uint64_t) (tp->hi - tp->lo), fetch,
                          reads_origin))
         return MPIX_REDOP_ERR_BUFFER;
-    if (opi < kOpReplace && !typed_entry(opi, tp->it))
+    // plan_entry answers for typed_entry, and for gpu_entry / getacc_entry, which
+    // a plan of one run launches through: every family is built from the one
+    // (type, op) table (redop_tables.h), so one lookup answers for all
+    if (opi < kOpReplace && !plan_entry(opi, tp->it))
         return MPIX_REDOP_ERR_TYPE;     // a legal pair without a kernel
     *n = tp->total;
     return MPIX_REDOP_SUCCESS;
@@ -2937,28 +2546,31 @@ static int typed_validate(const TypedSide &o, const TypedSide &r, const void *ta
 
 // Validated arguments: operand placement, the device's tables, the launches on
 // `s` -- one per residue group of the target plan; with no table on any side,
-// the contiguous entries' path with each buffer at its run's offset.
-static int typed_enqueue(const TypedSide &o, const TypedSide &r, void *target, MPIX_Iov_plan_s *tp,
-                         uint32_t op, bool fetch, hipStream_t s)
+// the contiguous entries' path with each buffer at its run's offset.  typed:
+// the typed entries' kernels (k_typed_*), which take the sides' packed-order
+// tables; else the plan entries' (k_plan_*), whose sides are packed.
+static int plan_enqueue(const TypedSide &o, const TypedSide &r, void *target, MPIX_Iov_plan_s *tp,
+                        uint32_t op, bool fetch, bool reads_origin, bool typed, hipStream_t s)
 {
     const uint32_t opi = op & 0xf;
-    const bool reads_origin = opi != kOpNoOp;
     Placed q{o.buf, r.buf, target};
     if (!place_operands(&q, fetch, false, reads_origin, s))
         return MPIX_REDOP_ERR_BUFFER;
     if (!fetch && opi == kOpNoOp)
         return MPIX_REDOP_SUCCESS;
     const bool otab = reads_origin && o.table(), rtab = fetch && r.table();
-    const char *po = reads_origin ? (const char *) q.origin + o.one_off() : nullptr;
-    char *pr = fetch ? (char *) q.result + r.one_off() : nullptr;
+    const char *po = (const char *) q.origin + o.one_off();
+    char *pr = (char *) q.result + r.one_off();
     if (tp->nrun == 1 && !otab && !rtab) {
         char *t1 = (char *) q.target + tp->one_off;
         if (!fetch)
             return enqueue(Combine{po, t1, tp->total, tp->it, tp->ext, op}, s, q.zc);
         return getacc_launch(po, pr, t1, tp->total, 1, 1, tp->it, tp->ext, opi, q.zc, s);
     }
-    const mpix::TypedEntry *en = opi < kOpReplace ? typed_entry(opi, tp->it) : nullptr;
-    if (opi < kOpReplace && !en)
+    const bool copies = opi >= kOpReplace;      // MPI_REPLACE, MPI_NO_OP: the copy kernels
+    const mpix::PlanEntry *pe = typed || copies ? nullptr : plan_entry(opi, tp->it);
+    const mpix::TypedEntry *te = typed && !copies ? typed_entry(opi, tp->it) : nullptr;
+    if (!copies && !pe && !te)
         return MPIX_REDOP_ERR_TYPE;
     const int dev = q.launch == -2 ? stream_device(s) : q.launch;
     char *tab = nullptr, *otb = nullptr, *rtb = nullptr;
@@ -2974,75 +2586,114 @@ static int typed_enqueue(const TypedSide &o, const TypedSide &r, void *target, M
                        rtab ? mpix::PackedTab(rtb, r.plan->nrun) : mpix::PackedTab()};
     PairMap pm{0, 0};
     (void) padded_pair(tp->it, &pm);
+    const mpix::CopyMode mode = copy_mode(opi, fetch);
+    const uint32_t ext = (uint32_t) tp->ext;
     auto launch = [&](void *tg) {
-        if (!en)
-            return hip_err(mpix::launch_typed_copy(copy_mode(opi, fetch), (uint32_t) tp->ext,
-                                                   pm.value_bytes, pm.loc_off, po, pr, tg, tr,
-                                                   launch_cfg(), s));
-        if (fetch)
-            return hip_err(en->getacc(po, pr, tg, tr, params(), launch_cfg(), s));
-        return hip_err(en->acc(po, tg, tr, params(), launch_cfg(), s));
+        if (typed && copies)
+            return hip_err(mpix::launch_typed_copy(mode, ext, pm.value_bytes, pm.loc_off, po, pr, tg,
+                                                   tr, launch_cfg(), s));
+        if (typed)
+            return hip_err(fetch ? te->getacc(po, pr, tg, tr, params(), launch_cfg(), s)
+                                 : te->acc(po, tg, tr, params(), launch_cfg(), s));
+        if (copies)
+            return hip_err(mpix::launch_plan_copy(mode, ext, pm.value_bytes, pm.loc_off, po, pr, tg,
+                                                  tr.d_tab, tr.d_tile, tr.nseg, tr.total,
+                                                  launch_cfg(), s));
+        return hip_err(fetch ? pe->getacc(po, pr, tg, tr.d_tab, tr.d_tile, tr.nseg, tr.total,
+                                          params(), launch_cfg(), s)
+                             : pe->reduce(po, tg, tr.d_tab, tr.d_tile, tr.nseg, tr.total, params(),
+                                          launch_cfg(), s));
     };
-    if (tp->nrun == 1)
+    if (tp->nrun == 1)      // typed only: a side has a table
         return launch((char *) q.target + tp->one_off);
-    const int32_t *tiles = (const int32_t *) (tab + tp->rt.tab.size() * sizeof(int64_t));
-    for (size_t g = 0; g < tp->rt.resid.size() && rc == MPIX_REDOP_SUCCESS; ++g) {
-        const ResidueGroup gr(tp->rt, g, (const int64_t *) tab);
+    return tp->each_group(tab, [&](const ResidueGroup &gr) {
         tr.d_tab = gr.seg_off;      // the group's whole table
-        tr.d_tile = tiles + tp->tile_base[g];
+        tr.d_tile = gr.tile;
         tr.nseg = gr.n;
         tr.total = gr.total;
-        rc = launch((char *) q.target + gr.resid);
-    }
-    return rc;
-}
-
-// Either form of the accumulate (fetch = false, no result) and of the fetch entry.
-static int typed_run(const void *origin, MPIX_Iov_plan origin_plan, void *result,
-                     MPIX_Iov_plan result_plan, void *target, MPIX_Iov_plan target_plan, uint32_t op,
-                     bool fetch, bool sync, hipStream_t stream)
-{
-    // under MPI_NO_OP neither origin nor origin_plan is looked at
-    const bool reads_origin = (op & 0xf) != kOpNoOp;
-    const TypedSide o{reads_origin ? origin : nullptr, reads_origin ? origin_plan : nullptr},
-        r{result, result_plan};
-    uint64_t n;
-    int rc = typed_validate(o, r, target, target_plan, op, fetch, &n);
-    if (rc != MPIX_REDOP_SUCCESS || n == 0)
-        return rc;
-    return on_stream(sync, stream, target, [&](hipStream_t s) {
-        return typed_enqueue(o, r, target, target_plan, op, fetch, s);
+        return launch((char *) q.target + gr.resid);
     });
 }
 
+// Every form of the plan entries (typed = false: origin and result packed, no
+// side plan) and of the typed entries.  The origin is an operand unless the op
+// is MPI_NO_OP -- for the plan entries only in their fetch form; the typed
+// entries then look at neither origin nor origin_plan.
+static int plan_run(const void *origin, MPIX_Iov_plan origin_plan, void *result,
+                    MPIX_Iov_plan result_plan, void *target, MPIX_Iov_plan target_plan, uint32_t op,
+                    bool fetch, bool typed, bool sync, hipStream_t stream)
+{
+    const bool noop = (op & 0xf) == kOpNoOp;
+    const bool reads_origin = !(noop && (typed || fetch));
+    const TypedSide o{typed && noop ? nullptr : origin, noop ? nullptr : origin_plan},
+        r{result, result_plan};
+    uint64_t n;
+    int rc = plan_validate(o, r, target, target_plan, op, fetch, reads_origin, &n);
+    if (rc != MPIX_REDOP_SUCCESS || n == 0)
+        return rc;
+    return on_stream(sync, stream, target, [&](hipStream_t s) {
+        return plan_enqueue(o, r, target, target_plan, op, fetch, reads_origin, typed, s);
+    });
+}
+
+int MPIX_Reduce_local_plan_async(const void *inbuf, void *inoutbuf, MPIX_Iov_plan plan, MPIX_Op op,
+                                 void *stream)
+{
+    return set_err(plan_run(inbuf, nullptr, nullptr, nullptr, inoutbuf, plan, (uint32_t) op,
+                            false, false, false, (hipStream_t) stream));
+}
+
+int MPIX_Reduce_local_plan(const void *inbuf, void *inoutbuf, MPIX_Iov_plan plan, MPIX_Op op)
+{
+    return set_err(plan_run(inbuf, nullptr, nullptr, nullptr, inoutbuf, plan, (uint32_t) op,
+                            false, false, true, nullptr));
+}
+
+int MPIX_Get_accumulate_local_plan_async(const void *origin, void *result, void *target,
+                                         MPIX_Iov_plan plan, MPIX_Op op, void *stream)
+{
+    return set_err(plan_run(origin, nullptr, result, nullptr, target, plan, (uint32_t) op, true,
+                            false, false, (hipStream_t) stream));
+}
+
+int MPIX_Get_accumulate_local_plan(const void *origin, void *result, void *target,
+                                   MPIX_Iov_plan plan, MPIX_Op op)
+{
+    return set_err(plan_run(origin, nullptr, result, nullptr, target, plan, (uint32_t) op, true,
+                            false, true, nullptr));
+}
+
+// ------------------------------------- a datatype on every side
+// MPIX_[Get_]accumulate_local_typed*: origin and result as plans too (NULL:
+// packed); plan_run with typed = true.
 int MPIX_Accumulate_local_typed_async(const void *origin, MPIX_Iov_plan origin_plan, void *target,
                                       MPIX_Iov_plan target_plan, MPIX_Op op, void *stream)
 {
-    return set_err(typed_run(origin, origin_plan, nullptr, nullptr, target, target_plan,
-                             (uint32_t) op, false, false, (hipStream_t) stream));
+    return set_err(plan_run(origin, origin_plan, nullptr, nullptr, target, target_plan,
+                            (uint32_t) op, false, true, false, (hipStream_t) stream));
 }
 
 int MPIX_Accumulate_local_typed(const void *origin, MPIX_Iov_plan origin_plan, void *target,
                                 MPIX_Iov_plan target_plan, MPIX_Op op)
 {
-    return set_err(typed_run(origin, origin_plan, nullptr, nullptr, target, target_plan,
-                             (uint32_t) op, false, true, nullptr));
+    return set_err(plan_run(origin, origin_plan, nullptr, nullptr, target, target_plan,
+                            (uint32_t) op, false, true, true, nullptr));
 }
 
 int MPIX_Get_accumulate_local_typed_async(const void *origin, MPIX_Iov_plan origin_plan,
                                           void *result, MPIX_Iov_plan result_plan, void *target,
                                           MPIX_Iov_plan target_plan, MPIX_Op op, void *stream)
 {
-    return set_err(typed_run(origin, origin_plan, result, result_plan, target, target_plan,
-                             (uint32_t) op, true, false, (hipStream_t) stream));
+    return set_err(plan_run(origin, origin_plan, result, result_plan, target, target_plan,
+                            (uint32_t) op, true, true, false, (hipStream_t) stream));
 }
 
 int MPIX_Get_accumulate_local_typed(const void *origin, MPIX_Iov_plan origin_plan, void *result,
                                     MPIX_Iov_plan result_plan, void *target,
                                     MPIX_Iov_plan target_plan, MPIX_Op op)
 {
-    return set_err(typed_run(origin, origin_plan, result, result_plan, target, target_plan,
-                             (uint32_t) op, true, true, nullptr));
+    return set_err(plan_run(origin, origin_plan, result, result_plan, target, target_plan,
+                            (uint32_t) op, true, true, true, nullptr));
 }
 
 // ------------------------------------- element-atomic accumulate

@@ -33,7 +33,7 @@ all: $(OUT)/coll_host_sanitize
 $(KOBJS):
 	$(MAKE) -s
 
-$(OUT)/%.o: %.cpp ../../include/mpix_redop.h ../../include/mpix_coll.h redop_dispatch.h redop_launch.h redop_hostpath.h redop_packed.h
+$(OUT)/%.o: %.cpp ../../include/mpix_redop.h ../../include/mpix_coll.h redop_dispatch.h redop_launch.h redop_hostpath.h redop_packed.h redop_runs.h
 	@mkdir -p $(OUT)
 	$(CXX) $(HOSTFLAGS) $(SANFLAGS) -c $< -o $@
 
